@@ -23,6 +23,13 @@ Multi-GPU (torchrun, one process per GPU, RCCL): weak scaling, each rank rolls o
 block of walks with no data-path collective; the CoM all-gather that reassembles the full
 trajectories is timed separately (allgather_ms), outside `value`.
 
+A plain run (`--gpus 1 --steps K --warmup W`) sets up, warms up, times the K launches and
+prints the headline line (`value`, `ms_per_step`, the roofline figures of those launches).
+`--full` adds everything that takes work of its own: the CPU baselines, the parity against the
+reference fixtures, the plan-build record, the dense-correlation and PCIe-inclusive timings
+and, for config 2, the config-3 `strict` and config-6 `herdt` sub-records.
+`--dump-outputs DIR` writes what the last timed launch returned as DIR/<name>.npy.
+
 Prints ONE JSON line (rank 0).
 """
 import argparse
@@ -57,6 +64,7 @@ HBM_PEAK_GBS = 8000.0   # MI355X_MICROARCH.md: HBM3E 8.0 TB/s (spec)
 FP64_PEAK_TFS = 78.6    # FP64 vector = matrix peak (spec)
 FP64_SUSTAINED_TFS = 56.6  # profiles/r1_fp64_peak.log: register-only FMA chains, 8 waves/SIMD
 SEED = 20251226
+DUMP_MAX_BYTES = 60 * 1000 * 1000  # --dump-outputs: all files together stay under 64 MB
 SPARSE_MAX = 40  # rollout.hip kSparseMax: z_ref changes per axis the sparse correlation takes
 SPARSE_MAX_WIDE = 64  # kSparseMaxWide: the same for the wide kernel (walks > 513 samples)
 # strict_lq.hip FLOP per instance-slot of one active-set pass (fma = 2, the z-input form of
@@ -160,6 +168,9 @@ def herdt_bench(args, rank, world, dev, dist_on):
     cnt = plan.counters(reset=True)
     hist, foot, status = last["out"]
     assert int(status.abs().max()) == 0, "solver reported a failed instance"
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, rank, [("hist", hist), ("foot", foot),
+                                               ("status", status)])
     solves_per_step = B * (n - 1) * world
     value = solves_per_step * args.steps / elapsed
     # algorithmic FP64 work per active-set pass, row and axis at the window's footstep count m
@@ -175,13 +186,13 @@ def herdt_bench(args, rank, world, dev, dist_on):
         return None
     com_rmse_ref = None
     gold = os.path.join(ROOT, "tests", "golden", "herdt_default.npz")
-    if os.path.exists(gold):
+    if args.full and os.path.exists(gold):
         g = np.load(gold)
         if g["com"].shape[0] == n:
             com_rmse_ref = float(np.sqrt(np.mean((hist[0, :, :, 0].cpu().numpy() - g["com"])
                                                  ** 2)))
     cpu = None
-    if world == 1 and not args.no_cpu_baseline:
+    if args.full and world == 1 and not args.no_cpu_baseline:
         cpu = _herdt_cpu_baseline(cfg, v_ref, st, hist.cpu().numpy(), foot.cpu().numpy(),
                                   x0_h, kick_h, args.cpu_seconds)
     return {
@@ -610,6 +621,27 @@ def timed_region(launch, steps, collective, dev):
     return elapsed, (ev0.elapsed_time(ev1) / steps if cuda else None)
 
 
+def dump_outputs(dirname, rank, arrays):
+    """`--dump-outputs DIR`: the per-walk arrays [(name, tensor [B, ...])] the last timed launch
+    returned, as DIR/<name>.npy in float64 (rank r > 0: <name>.rank<r>.npy).  Within
+    DUMP_MAX_BYTES in all: a larger batch is cut to a fixed sample of its walks (the same
+    walks for the same batch size, ascending; their indices go to DIR/sample_walks.npy), so
+    two builds run with the same arguments write arrays that compare element for element."""
+    os.makedirs(dirname, exist_ok=True)
+    B = arrays[0][1].shape[0]
+    per_walk = 8 + sum(8 * (t.numel() // B) for _, t in arrays)
+    k = min(B, (DUMP_MAX_BYTES - 128 * (len(arrays) + 1)) // per_walk)
+    idx = np.arange(B)
+    if k < B:
+        idx = np.sort(np.random.default_rng(SEED).choice(B, k, replace=False))
+    suffix = "" if rank == 0 else f".rank{rank}"
+    for name, t in arrays:
+        sel = t[torch.as_tensor(idx, device=t.device)]
+        np.save(os.path.join(dirname, f"{name}{suffix}.npy"),
+                sel.to(torch.float64).cpu().numpy())
+    np.save(os.path.join(dirname, f"sample_walks{suffix}.npy"), idx.astype(np.float64))
+
+
 def gather_com(com, total, world, dev):
     """All-gather of the per-rank CoM blocks (RCCL over xGMI on GPUs): (full [total, ...],
     milliseconds), timed separately from `value`."""
@@ -785,6 +817,16 @@ def main():
     ap.add_argument("--horizon", type=int, default=None)
     ap.add_argument("--strict", action="store_true", help="alias of --config 3")
     ap.add_argument("--unconstrained", action="store_true", help="config 4 unconstrained variant")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline: the CPU baselines, the parity against the "
+                         "reference fixtures, the plan-build record, the dense-correlation and "
+                         "PCIe-inclusive timings and (config 2) the strict and Herdt sub-records; "
+                         "a run without it sets up, warms up, times --steps launches and prints "
+                         "the line")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last timed launch returned as "
+                         "DIR/<name>.npy (float64; a fixed seeded sample of the walks when the "
+                         "whole batch is larger than 64 MB)")
     ap.add_argument("--cpu-seconds", type=float, default=10.0)
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--dist-backend", default="nccl", choices=("nccl", "gloo"),
@@ -807,12 +849,12 @@ def main():
                          "value; off by default so a profile of the default command sees only "
                          "non-overlapped launches)")
     ap.add_argument("--strict-steps", type=int, default=3,
-                    help="default line (config 2): timed launches of the config-3 strict "
+                    help="--full line (config 2): timed launches of the config-3 strict "
                          "sub-record (0 = no sub-record)")
     ap.add_argument("--strict-cpu-seconds", type=float, default=4.0,
                     help="CPU-leg budget per process of the strict sub-record")
     ap.add_argument("--herdt-steps", type=int, default=3,
-                    help="default line (config 2): timed launches of the config-6 Herdt "
+                    help="--full line (config 2): timed launches of the config-6 Herdt "
                          "sub-record (0 = no sub-record)")
     ap.add_argument("--herdt-cpu-seconds", type=float, default=4.0,
                     help="CPU-leg budget per process of the Herdt sub-record")
@@ -868,13 +910,14 @@ def main():
         line = herdt_bench(args, rank, world, dev, dist_on)
     else:
         line = rollout_bench(args, conf, rank, world, dev, dist_on)
-        if conf == 2 and args.strict_steps > 0 and not args.batch and not args.horizon:
+        subs = args.full and conf == 2 and not args.batch and not args.horizon
+        if subs and args.strict_steps > 0:
             # the strict experiment (run_compare_resistance.py:87-169; default.json:18
             # "strict": true) beside the headline: config 3 in its own timed region
             sub = strict_subrecord(args, rank, world, dev, dist_on)
             if rank == 0:
                 line["strict"] = sub
-        if conf == 2 and args.herdt_steps > 0 and not args.batch and not args.horizon:
+        if subs and args.herdt_steps > 0:
             # the Herdt experiment (zmp_controller.py:435-826, config 6) likewise
             sub = herdt_subrecord(args, rank, world, dev, dist_on)
             if rank == 0:
@@ -887,14 +930,14 @@ def main():
 
 def strict_subrecord(args, rank, world, dev, dist_on):
     """Config 3 (B = 65 536 walks per GPU, N = 150, strict, f64) as a sub-record of the default
-    line: its own warm-up and timed region (barrier + synchronize on both sides, max over
+    workload's `--full` line: its own warm-up and timed region (barrier + synchronize on both sides, max over
     ranks), roofline (counted FP64 work, algorithmic bytes, PMC traffic) and, at one GPU, the
     CPU legs with a shorter budget.  The headline `value` stays config 2's."""
     sa = argparse.Namespace(**vars(args))
     sa.steps, sa.warmup = args.strict_steps, 1
     sa.batch, sa.horizon, sa.option = None, None, []
     sa.unconstrained, sa.pipelined, sa.no_dense_leg = False, False, True
-    sa.cpu_seconds = args.strict_cpu_seconds
+    sa.cpu_seconds, sa.dump_outputs = args.strict_cpu_seconds, None
     sub = rollout_bench(sa, 3, rank, world, dev, dist_on)
     if rank != 0:
         return None
@@ -905,12 +948,12 @@ def strict_subrecord(args, rank, world, dev, dist_on):
 
 def herdt_subrecord(args, rank, world, dev, dist_on):
     """Config 6 (32 768 Herdt walks per GPU, N = 150, f64) as a second sub-record of the default
-    line, built like `strict_subrecord`: its own warm-up and timed region, roofline and, at one
+    workload's `--full` line, built like `strict_subrecord`: its own warm-up and timed region, roofline and, at one
     GPU, the CPU legs with a shorter budget."""
     sa = argparse.Namespace(**vars(args))
     sa.steps, sa.warmup = args.herdt_steps, 1
     sa.batch, sa.horizon = None, None
-    sa.cpu_seconds = args.herdt_cpu_seconds
+    sa.cpu_seconds, sa.dump_outputs = args.herdt_cpu_seconds, None
     sub = herdt_bench(sa, rank, world, dev, dist_on)
     if rank != 0:
         return None
@@ -933,7 +976,7 @@ def rollout_bench(args, conf, rank, world, dev, dist_on):
     n = zmax_h.shape[-2]
     kick_h = cfg.dt * F_h / cfg.m
     plan = Plan(dev.index, cfg.horizon, cfg.dt, cfg.h, cfg.g, cfg.Q, cfg.R, cfg.strict)
-    plan_rec = plan_record(plan)
+    plan_rec = plan_record(plan) if args.full else None
     for o in args.option:
         name, _, val = o.partition("=")
         plan.set_option(name, int(val))
@@ -955,6 +998,8 @@ def rollout_bench(args, conf, rank, world, dev, dist_on):
     elapsed, kern_ms = timed_region(launch, args.steps, dist_on, dev)
     work = plan.counters() if cfg.strict else None
     assert int(status.abs().max()) == 0, "solver reported a failed instance"
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, rank, [("hist", hist), ("status", status)])
 
     solves_per_step = B * (n - 1) * 2 * world
     value = solves_per_step * args.steps / elapsed
@@ -979,7 +1024,7 @@ def rollout_bench(args, conf, rank, world, dev, dist_on):
     # parity in the same run: the reference walk (walk 0 of rank 0) vs the committed
     # reference fixture (tests/golden: produced by the reference itself)
     com_rmse_ref = None
-    if rank == 0 and cfg.horizon == 150:
+    if args.full and rank == 0 and cfg.horizon == 150:
         fx = np.load(os.path.join(ROOT, "tests", "golden", "walk_n150.npz"))
         ref_com = fx["com_force"]
         if cfg.strict and not wl["shared"]:
@@ -995,7 +1040,8 @@ def rollout_bench(args, conf, rank, world, dev, dist_on):
     # axis_correlate_sparse) for waves whose axis has ≤ 40 z_ref changes, else dense.  The dense
     # form is timed on the same inputs beside it (plan option ZMPC_OPT_CORRELATION = 1)
     corr = None
-    if rank == 0 and not cfg.strict and not wl["shared"] and not args.no_dense_leg:
+    if (args.full and rank == 0 and not cfg.strict and not wl["shared"]
+            and not args.no_dense_leg):
         zr = (zmax_h + zmin_h) / 2
         ch = np.count_nonzero(np.diff(zr, axis=1), axis=1)  # [B, 2] changes per walk and axis
         wide = n - 1 > 512  # wide kernel: its own limit, and a walk is sparse if both axes are
@@ -1058,7 +1104,7 @@ def rollout_bench(args, conf, rank, world, dev, dist_on):
 
     # the drop-in batch API hands host arrays over: PCIe-inclusive rate (never `value`)
     pcie = None
-    if rank == 0 and world == 1:
+    if args.full and rank == 0 and world == 1:
         reps = 1 if cfg.strict else 3
         torch.cuda.synchronize()
         tp = time.perf_counter()
@@ -1072,7 +1118,7 @@ def rollout_bench(args, conf, rank, world, dev, dist_on):
                         "kernel, D2H of the history"}
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         cpu = cpu_baseline(zmax_h, zmin_h, x0_h, kick_h, hist.cpu().numpy(), cfg,
                            args.cpu_seconds)
 

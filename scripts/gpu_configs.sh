@@ -5,7 +5,7 @@ OUT=gpurun_out/${1:-configs}
 mkdir -p "$OUT"
 run() {  # name, timeout, args...
   local name=$1 t=$2; shift 2
-  timeout -k 10 "$t" python3 bench.py "$@" > "$OUT/$name.json" 2> "$OUT/$name.err"
+  timeout -k 10 "$t" python3 bench.py --full "$@" > "$OUT/$name.json" 2> "$OUT/$name.err"
   local rc=$?
   echo "== $name rc=$rc"; [ $rc -ne 0 ] && { tail -5 "$OUT/$name.err"; exit $rc; }
   return 0

@@ -114,3 +114,36 @@ def test_bench_harness_cpu_leg_semantics():
     for strict in (False, True):
         t = bench.harness_cpu_seconds(10, strict)
         assert 0.0 < t < 1.0
+
+
+def test_bench_dump_outputs_whole_and_sampled(tmp_path, monkeypatch):
+    """bench.dump_outputs (`--dump-outputs DIR`): float64 DIR/<name>.npy of the per-walk arrays;
+    under the size limit the whole batch, above it the same ascending sample of walks on every
+    call, every array cut to those walks, all files together within the limit."""
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    if root not in sys.path:
+        sys.path.insert(0, root)
+    import bench
+    B, n = 37, 5
+    hist = (torch.arange(B, dtype=torch.float64)[:, None, None, None] +
+            torch.arange(n * 6, dtype=torch.float64).reshape(n, 2, 3) / 64.0)
+    status = torch.arange(B, dtype=torch.int32)
+    arrays = [("hist", hist), ("status", status)]
+    whole = tmp_path / "whole"
+    bench.dump_outputs(str(whole), 0, arrays)
+    assert np.array_equal(np.load(whole / "hist.npy"), hist.numpy())
+    assert np.load(whole / "status.npy").dtype == np.float64
+    assert np.array_equal(np.load(whole / "sample_walks.npy"), np.arange(B))
+    limit = 128 * 3 + 11 * (8 + 8 + 8 * n * 6)   # room for 11 of the 37 walks
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", limit)
+    a, b = tmp_path / "a", tmp_path / "b"
+    bench.dump_outputs(str(a), 0, arrays)
+    bench.dump_outputs(str(b), 0, arrays)
+    w = np.load(a / "sample_walks.npy")
+    assert len(w) == 11 and np.all(np.diff(w) > 0) and w[-1] < B
+    assert np.array_equal(np.load(a / "hist.npy"), hist.numpy()[w.astype(int)])
+    assert np.array_equal(np.load(a / "status.npy"), w)
+    assert sum(os.path.getsize(a / f) for f in os.listdir(a)) <= limit
+    for f in os.listdir(a):
+        assert np.array_equal(np.load(a / f), np.load(b / f))
