@@ -197,6 +197,40 @@ int zmpc_rollout_kicks(const zmpc_plan* plan, int64_t B, int64_t n, const double
                        int32_t* status, void* stream);
 
 /*
+ * Per-walk robustness metrics of a state history, reduced on the device: the ZMP estimate
+ * z = C·state = c − (h/g)·c̈ of run_mpc.py:294 held against the support box of its own sample,
+ * as run_compare_resistance.py:173-197 plots the two (sample i with bounds row i) for the eye
+ * to judge.  Replaces that plot-and-look step, and the chain of [B, n, 2] temporaries (or the
+ * copy of hist to the host) that the same figures cost when built from array operations.
+ *   hist       : [B, n, 2, 3]  state history of zmpc_rollout / zmpc_rollout_kicks /
+ *                              zmpc_herdt_rollout, (c, ċ, c̈) per axis (a = 0: x, a = 1: y)
+ *   zmax, zmin : [B, n, 2]     the walks' CoP bounds; bounds_stride as zmpc_rollout (2n or
+ *                              more doubles between walks, 0 = one CoP for every walk)
+ *   lengths    : [B] int64 or NULL  live samples n_b of ragged walks, 1 <= n_b <= n (a value
+ *                              outside is clamped); rows at or past n_b are never read into a
+ *                              result.  NULL: n_b = n
+ *   metrics    : [B, ZMPC_NMETRICS]  per walk, slot 2k + a = quantity k of axis a.  With
+ *                              zr = (zmax + zmin)/2 and v = max(z − zmax, zmin − z, 0) of
+ *                              sample i against bounds row i, over 0 <= i < n_b:
+ *     [0,1]   viol_max     max v
+ *     [2,3]   viol_argmax  the smallest i that attains it, as a double; −1 when viol_max is 0
+ *     [4,5]   viol_count   samples with v > 0
+ *     [6,7]   com_dev_max  max |c − zr|
+ *     [8,9]   zmp_rms      sqrt(mean (z − zr)²)
+ *     [10,11] dcm_end      c + ċ·sqrt(h/g) − zr at i = n_b − 1: the divergent component of
+ *                          motion at the last sample, relative to the final box centre
+ * An axis with a non-finite state value in a live sample reports viol_max = +inf, viol_argmax =
+ * the first such sample and NaN in its other slots (a threshold on viol_max fails safe); the
+ * other axis and the other walks are unaffected.  The reductions run in a fixed order: two calls
+ * on the same input agree bit for bit.  Any plan of the device serves, strict or not: only its
+ * h/g is read.  No workspace, no status array.  Additive to ABI 7.
+ */
+#define ZMPC_NMETRICS 12
+int zmpc_walk_metrics(const zmpc_plan* plan, int64_t B, int64_t n, const double* hist,
+                      const double* zmax, const double* zmin, int64_t bounds_stride,
+                      const int64_t* lengths, double* metrics, void* stream);
+
+/*
  * Batched CoP-bound producer: CoPGenerator.generate_cop_trajectory
  * (generators/cop_generator.py:34-115) over the footstep plan of
  * generators/footstep_generator.py:19-49, one walk per set of parameters.

@@ -382,6 +382,26 @@ int zmpc_rollout_kicks(const zmpc_plan* P, int64_t B, int64_t n, const double* z
                       status, stream);
 }
 
+int zmpc_walk_metrics(const zmpc_plan* P, int64_t B, int64_t n, const double* hist,
+                      const double* zmax, const double* zmin, int64_t bounds_stride,
+                      const int64_t* lengths, double* metrics, void* stream) {
+  g_err.clear();
+  if (!P) return fail(ZMPC_EINVAL, "NULL plan");
+  if (B < 0 || n < 1) return fail(ZMPC_EINVAL, "need B >= 0 and n >= 1");
+  if (bounds_stride != 0 && bounds_stride < 2 * n)
+    return fail(ZMPC_EINVAL, "bounds_stride must be 0 (shared CoP) or >= 2n");
+  if (B == 0) return ZMPC_OK;
+  if (!hist || !zmax || !zmin || !metrics) return fail(ZMPC_EINVAL, "NULL array argument");
+  if (B > 0x7fffffff) return fail(ZMPC_EINVAL, "batch too large");
+  if (n > (1 << 24)) return fail(ZMPC_EINVAL, "walk too long");
+  DeviceGuard g(P->device);
+  if (g.err != hipSuccess) return hip_fail(g.err, "hipSetDevice");
+  hipError_t e = zmpc_launch_walk_metrics(P, B, n, hist, zmax, zmin, bounds_stride, lengths,
+                                          metrics, (hipStream_t)stream);
+  if (e != hipSuccess) return hip_fail(e, "zmpc_walk_metrics launch");
+  return ZMPC_OK;
+}
+
 static int herdt_check(const zmpc_plan* P, const zmpc_herdt_params* prm, int64_t B) {
   if (!P || !prm) return fail(ZMPC_EINVAL, "NULL plan or params");
   if (B < 0) return fail(ZMPC_EINVAL, "B < 0");

@@ -100,6 +100,12 @@ hipError_t zmpc_launch_plan(zmpc_plan* p, hipStream_t s, hipEvent_t* ev);
 hipError_t zmpc_launch_cop(int64_t B, const double* params, int64_t n_cap, double* zmax,
                            double* zmin, int8_t* states, int64_t* n_out, hipStream_t s);
 
+// per-walk robustness metrics of a state history (metrics.hip): one wavefront per walk, reads
+// only p->hg and p->cus; lengths may be NULL (every walk has n live samples)
+hipError_t zmpc_launch_walk_metrics(const zmpc_plan* p, int64_t B, int64_t n, const double* hist,
+                                    const double* zmax, const double* zmin, int64_t bstride,
+                                    const int64_t* lengths, double* metrics, hipStream_t s);
+
 // unconstrained rollout / step (rollout.hip)
 hipError_t zmpc_launch_rollout_unc(const zmpc_plan* p, int64_t B, int64_t n, const double* zmax,
                                    const double* zmin, int64_t bstride, const double* x0,

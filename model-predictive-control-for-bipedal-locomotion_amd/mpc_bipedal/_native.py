@@ -19,6 +19,7 @@ PLAN_STAGE_NAMES = ("prediction", "gram_PuTPu", "cholesky", "gain", "scan", "fft
                     "strict_X", "strict_gram_G", "strict_Pu_inverse", "strict_gram_Hz",
                     "strict_lq_table", "total")
 HERDT_MAX_FACETS = 16  # include/zmpc.h ZMPC_HERDT_MAX_FACETS
+NMETRICS = 12    # include/zmpc.h ZMPC_NMETRICS
 
 ZMPC_OK = 0
 ZMPC_EINVAL = -1
@@ -66,6 +67,9 @@ SIGNATURES = {
                                           _c_dbl_p, _c_dbl_p, ctypes.c_int64, _c_dbl_p, _c_dbl_p,
                                           ctypes.c_void_p, _c_dbl_p, ctypes.c_void_p,
                                           ctypes.c_void_p]),
+    "zmpc_walk_metrics": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64,
+                                         _c_dbl_p, _c_dbl_p, _c_dbl_p, ctypes.c_int64,
+                                         ctypes.c_void_p, _c_dbl_p, ctypes.c_void_p]),
     "zmpc_cop_generate": (ctypes.c_int, [ctypes.c_int, ctypes.c_int64, _c_dbl_p, ctypes.c_int64,
                                          _c_dbl_p, _c_dbl_p, ctypes.c_void_p, ctypes.c_void_p,
                                          ctypes.c_void_p]),

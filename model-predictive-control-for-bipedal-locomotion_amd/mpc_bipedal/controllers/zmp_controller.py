@@ -12,7 +12,9 @@ The Herdt joint footstep QP (``method="herdt"``, :203-531) runs on the device as
 
 Additions (not in the reference): ``generate_com_trajectory_batch`` /
 ``generate_state_trajectory_batch`` / ``generate_com_trajectory_herdt_batch`` for many walks or
-disturbance scenarios at once, taking and returning torch device tensors.
+disturbance scenarios at once, taking and returning torch device tensors; ``walk_metrics`` (did
+the ZMP stay inside the support box, per walk, reduced on the device) and ``critical_force``
+(the largest push each scenario survives, by bisection over batched rollouts).
 """
 
 import warnings
@@ -21,6 +23,7 @@ from typing import Optional, Tuple
 import numpy as np
 import torch
 
+from ..analysis import NMETRICS, WalkMetrics
 from ..config import MPCConfig
 from ..models.lipm_model import lipm_matrices
 from ..solver import get_plan
@@ -288,6 +291,107 @@ class ZMPController:
         if isinstance(hist, torch.Tensor):
             return hist @ torch.as_tensor(C, dtype=hist.dtype, device=hist.device)
         return np.asarray(hist) @ C
+
+    # ------------------------------------------------------------------ robustness analysis
+    def walk_metrics(self, hist, z_max, z_min, walk_lengths=None) -> WalkMetrics:
+        """Per-walk robustness metrics of a state history (addition; zmpc_walk_metrics): the ZMP
+        of run_mpc.py:294 against the support box of its sample, as
+        run_compare_resistance.py:173-197 plots them, reduced on the device.
+
+        hist [B,n,2,3] (a batch method's output; a NumPy array is staged to the device);
+        z_max, z_min [B,n,2] or a shared [n,2]; walk_lengths [B] live samples of ragged walks.
+        Returns analysis.WalkMetrics: named [B,2] (x, y) columns — viol_max, viol_argmax,
+        viol_count, com_dev_max, zmp_rms, dcm_end — over one [B,12] device tensor."""
+        plan = self._plan()
+        dev = torch.device("cuda", plan.device)
+        h = torch.as_tensor(hist, dtype=torch.float64, device=dev).contiguous()
+        return WalkMetrics(plan.walk_metrics(h, z_max, z_min, lengths=walk_lengths))
+
+    def critical_force(self, z_max, z_min, x_init=None, force_step=None, direction=+1,
+                       F_hi: float = 1000.0, iters: int = 30, max_violation: float = 1e-9,
+                       max_com_dev: Optional[float] = None,
+                       max_dcm_end: Optional[float] = None, walk_lengths=None):
+        """Largest push each scenario survives (addition): the question the F_ext sweep of
+        run_compare_resistance.py:87-169 puts to the eye, answered by bisection on the device.
+
+        B scenarios — from x_init [B,2,3], per-walk bounds [B,n,2], or a [B] force_step or
+        direction.  Scenario b is pushed at history step force_step[b] (default n//2, or
+        n_b//2 with walk_lengths) by direction[b]·F newtons on the y axis only, as the
+        reference pushes (zmp_controller.py:105-106).  A push passes when, on both axes,
+        viol_max <= max_violation and, where set, com_dev_max <= max_com_dev and
+        |dcm_end| <= max_dcm_end (and, on a strict plan, the solver reported no failure).
+        Bisection on F in [0, F_hi]: each of the iters + 2 evaluations is one batched rollout
+        into one reused history buffer, one walk_metrics launch and a torch.where on the
+        bracket; nothing is copied to the host.
+
+        Returns (F_lo, F_hi), [B] device tensors: the final bracket, F_lo passes and F_hi fails,
+        F_hi − F_lo = F_hi/2**iters.  NaN in both where the walk fails with no push at all;
+        F_lo = F_hi = the search limit where it passes even there.
+
+        Bisection assumes that pass/fail is monotone in F.  For the unconstrained controller
+        with a passing unpushed walk that is exact: the closed loop is linear, every ZMP sample
+        is affine in F, so the passing set is an interval that contains 0.  For strict plans
+        it is an assumption (the clamped ZMP hides the push until the QP fails or the CoM
+        criteria trip)."""
+        plan = self._plan()
+        dev = torch.device("cuda", plan.device)
+        f64 = dict(dtype=torch.float64, device=dev)
+        zmax_t = torch.as_tensor(z_max, **f64).contiguous()
+        zmin_t = torch.as_tensor(z_min, **f64).contiguous()
+        n = int(zmax_t.shape[-2])
+        sizes = [int(np.shape(a)[0]) for a in (force_step, direction, walk_lengths)
+                 if a is not None and np.ndim(a) == 1]
+        if x_init is not None:
+            x0 = torch.as_tensor(x_init, **f64)
+            B = int(x0.shape[0])
+        else:
+            B = int(zmax_t.shape[0]) if zmax_t.dim() == 3 else (sizes[0] if sizes else 1)
+            x0 = torch.zeros((B, 2, 3), **f64)
+        if any(s != B for s in sizes):
+            raise ValueError("force_step, direction and walk_lengths must be scalars or "
+                             f"[B] = [{B}]")
+        if not (F_hi > 0) or iters < 0:
+            raise ValueError("need F_hi > 0 and iters >= 0")
+        sign = torch.sign(torch.as_tensor(direction, **f64)).expand(B).contiguous()
+        lengths = None
+        if walk_lengths is not None:
+            lengths = torch.as_tensor(walk_lengths, dtype=torch.int64, device=dev).reshape(B)
+        if force_step is None:
+            step = (n // 2) if lengths is None else lengths // 2
+        elif np.ndim(force_step) == 0:
+            step = int(force_step)
+        else:
+            step = torch.as_tensor(force_step, dtype=torch.int64, device=dev)
+        kick = torch.zeros(B, **f64)
+        launch = plan.rollout_launcher(zmax_t, zmin_t, x0, kick=kick, kick_step=step)
+        metrics = torch.empty((B, NMETRICS), **f64)
+        m = WalkMetrics(metrics)
+        dt, mass = self.config.dt, self.config.m
+
+        def passes(F):
+            kick.copy_(dt * (sign * F) / mass)  # zmp_controller.py:106
+            launch()
+            plan.walk_metrics(launch.hist, zmax_t, zmin_t, lengths=lengths, out=metrics)
+            ok = (m.viol_max <= max_violation).all(dim=1)  # (+inf and NaN fail)
+            if max_com_dev is not None:
+                ok &= (m.com_dev_max <= max_com_dev).all(dim=1)
+            if max_dcm_end is not None:
+                ok &= (m.dcm_end.abs() <= max_dcm_end).all(dim=1)
+            if plan.strict:
+                ok &= launch.status == 0
+            return ok
+
+        top = torch.full((B,), float(F_hi), **f64)
+        lo = torch.zeros(B, **f64)
+        hi = top.clone()
+        never = ~passes(lo)
+        lo = torch.where(passes(top), top, lo)
+        for _ in range(int(iters)):
+            mid = 0.5 * (lo + hi)
+            ok = passes(mid)
+            lo, hi = torch.where(ok, mid, lo), torch.where(ok, hi, mid)
+        nan = torch.full_like(lo, float("nan"))
+        return torch.where(never, nan, lo), torch.where(never, nan, hi)
 
     # ------------------------------------------------------------------ internals
     def _rollout_host(self, x_init, y_init, z_max, z_min, kick, kick_step) -> np.ndarray:

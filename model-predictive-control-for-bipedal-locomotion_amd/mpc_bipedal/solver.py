@@ -224,6 +224,51 @@ class Plan:
                 _ptr(ks), _ptr(hist), _ptr(status))
         return hist, status, ("zmpc_rollout_kicks", args, (zmax, zmin, x0, kick_t, ks))
 
+    def walk_metrics(self, hist, zmax, zmin, lengths=None, out=None):
+        """Per-walk robustness metrics of a state history (zmpc_walk_metrics, include/zmpc.h)
+        → [B, 12] device tensor, slot 2k + a = quantity k (analysis.SLOT_NAMES) of axis a.
+
+        hist: a contiguous float64 [B, n, 2, 3] tensor on the plan's device (a rollout's
+        output; it is never copied); zmax/zmin: [B, n, 2] per-walk CoP bounds, or [n, 2] one
+        CoP shared by every walk; lengths: [B] live samples of ragged walks (1 <= n_b <= n) or
+        None; out: a contiguous float64 [B, 12] tensor on the plan's device to write into.
+        Asynchronous on the current stream.  Works on any plan: only h/g is read.
+        """
+        dev = self._dev()
+        if not isinstance(hist, torch.Tensor) or hist.dim() != 4 or hist.shape[2:] != (2, 3) \
+                or hist.dtype != torch.float64 or hist.device != dev or not hist.is_contiguous():
+            raise ValueError("hist must be a contiguous float64 [B, n, 2, 3] tensor on the "
+                             "plan's device")
+        B, n = int(hist.shape[0]), int(hist.shape[1])
+        if n < 1:
+            raise ValueError("hist must hold at least one sample per walk")
+        zmax = self._as_dev(zmax)
+        if zmax.dim() == 2:
+            shape, bstride = (n, 2), 0
+        else:
+            shape, bstride = (B, n, 2), 2 * n
+        if tuple(zmax.shape) != shape:
+            raise ValueError(f"z_max must be [B, n, 2] = [{B}, {n}, 2] or [n, 2], got "
+                             f"{tuple(zmax.shape)}")
+        zmin = self._as_dev(zmin, shape)
+        len_t = None
+        if lengths is not None:
+            len_t = torch.as_tensor(lengths, dtype=torch.int64, device=dev).contiguous()
+            if tuple(len_t.shape) != (B,):
+                raise ValueError(f"lengths must be [B] = [{B}], got {tuple(len_t.shape)}")
+        if out is None:
+            out = torch.empty((B, _native.NMETRICS), dtype=torch.float64, device=dev)
+        elif tuple(out.shape) != (B, _native.NMETRICS) or out.dtype != torch.float64 or \
+                out.device != dev or not out.is_contiguous():
+            raise ValueError(f"out must be a contiguous float64 [B, {_native.NMETRICS}] tensor "
+                             "on the plan's device")
+        with torch.cuda.device(self.device):
+            stream = torch.cuda.current_stream(self.device).cuda_stream
+            rc = _native.load().zmpc_walk_metrics(self._live(), B, n, _ptr(hist), _ptr(zmax),
+                                                  _ptr(zmin), bstride, _ptr(len_t), _ptr(out),
+                                                  ctypes.c_void_p(stream))
+        _native.check(rc, "zmpc_walk_metrics")
+        return out
 
     # -- Herdt joint footstep QP (zmpc_herdt_rollout / zmpc_herdt_step) --------------------
     def herdt_rollout(self, params, v_ref, states, nb_next, x0, kick=None, kick_step=-1):
