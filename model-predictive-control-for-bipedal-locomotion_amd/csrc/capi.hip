@@ -249,11 +249,13 @@ int zmpc_plan_set_option(zmpc_plan* P, int32_t option, int64_t value) {
   if (value < 0 || value > hi[option])
     return fail(ZMPC_EINVAL, "option value out of range (0.." + std::to_string(hi[option]) + ")");
   if (option == ZMPC_OPT_STRICT_SOLVER && (value == 1 || value == 2) &&
-      (!P->strict || P->N > 512))
-    return fail(ZMPC_EINVAL, "the reduced-Cholesky strict kernels need a strict plan, N <= 512");
+      (!P->strict || P->N > kStrictCholMaxN))
+    return fail(ZMPC_EINVAL, "the reduced-Cholesky strict kernels need a strict plan, N <= " +
+                                  std::to_string(kStrictCholMaxN));
   if (option == ZMPC_OPT_STRICT_SOLVER && value == 4 &&
       (!P->strict || !zmpc_strict_scan_supported(P)))
-    return fail(ZMPC_EINVAL, "the small-batch strict kernel needs a strict plan, N <= 960");
+    return fail(ZMPC_EINVAL, "the small-batch strict kernel needs a strict plan, N <= " +
+                                  std::to_string(kScanMaxN));
   if (option == ZMPC_OPT_STRICT_SOLVER && value == 3 && !zmpc_strict_lq_supported(P))
     return fail(ZMPC_EINVAL, "the LQ strict kernel needs a strict plan, N <= " +
                                   std::to_string(ZMPC_STRICT_MAX_N));
@@ -329,10 +331,9 @@ int zmpc_step(const zmpc_plan* P, int64_t B, const double* x, const double* zmax
   DeviceGuard g(P->device);
   if (g.err != hipSuccess) return hip_fail(g.err, "hipSetDevice");
   std::string why;
-  hipError_t e = P->strict ? zmpc_launch_step_strict(P, B, x, zmax_win, zmin_win, x_next, status,
-                                                     (hipStream_t)stream, &why)
-                           : zmpc_launch_step_unc(P, B, x, zmax_win, zmin_win, x_next, status,
-                                                  (hipStream_t)stream);
+  const StepCall c{B, x, zmax_win, zmin_win, x_next, status};
+  hipError_t e = P->strict ? zmpc_launch_step_strict(P, c, (hipStream_t)stream, &why)
+                           : zmpc_launch_step_unc(P, c, (hipStream_t)stream);
   return launch_result(e, why, "zmpc_step");
 }
 
@@ -353,12 +354,10 @@ static int rollout_impl(const zmpc_plan* P, int64_t B, int64_t n, const double* 
   if (g.err != hipSuccess) return hip_fail(g.err, "hipSetDevice");
   std::string why;
   hipStream_t s = (hipStream_t)stream;
-  hipError_t e = P->strict ? zmpc_launch_rollout_strict(P, B, n, zmax, zmin, bounds_stride, x0,
-                                                        kick, kick_step, kick_steps, hist,
-                                                        status, s, &why)
-                           : zmpc_launch_rollout_unc(P, B, n, zmax, zmin, bounds_stride, x0,
-                                                     kick, kick_step, kick_steps, hist, status,
-                                                     s, &why);
+  const RolloutCall c{B, n, zmax, zmin, bounds_stride, x0, kick, kick_step, kick_steps, hist,
+                      status};
+  hipError_t e = P->strict ? zmpc_launch_rollout_strict(P, c, s, &why)
+                           : zmpc_launch_rollout_unc(P, c, s, &why);
   return launch_result(e, why, "zmpc_rollout");
 }
 

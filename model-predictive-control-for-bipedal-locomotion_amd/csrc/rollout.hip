@@ -118,21 +118,6 @@ __device__ __forceinline__ void lipm_step(const LipmConsts& c, const double* x, 
   y[2] = x[2] + c.T * u;
 }
 
-// Correlation tile width: outputs per lane per pass, chosen per walk length so that
-// passes·64·CW barely covers the n−1 timesteps (n = 420 → CW = 7: 448 outputs, 1 pass).
-int pick_cw(int64_t nsteps) {
-  int best = 8;
-  int64_t best_cost = INT64_MAX;
-  for (int cw = 8; cw >= 1; --cw) {
-    const int64_t cost = ((nsteps + 64 * cw - 1) / (64 * cw)) * cw;
-    if (cost < best_cost) {
-      best_cost = cost;
-      best = cw;
-    }
-  }
-  return best;
-}
-
 // LDS layout of z_ref: lane l's chunk starts at t = l·CW; for even CW one pad double per CW
 // keeps the 64 lanes' ds_read_b64 on distinct banks (lane stride CW+1 doubles, odd).
 template <int CW>
@@ -156,44 +141,9 @@ struct HistLayout {
     return r * 6 + (r >= 1 ? kPad * ((r - 1) / kSpan) : 0);
   }
   __host__ __device__ static constexpr size_t doubles(int n) {
-    return (size_t)n * 6 + (size_t)kPad * ((n + kSpan - 1) / kSpan);
+    return hist_doubles(CW, n);  // (dispatch.h: it enters the launch rules' LDS sizes)
   }
 };
-
-struct RolloutGeom {
-  int cw, passes, kc, lz, lzp, nf;
-  int kfm;  // fast-FIR steps (odd CW; axis_correlate_ffa), 0 otherwise
-  int kcp;  // doubles of LDS for the staged gain row (kc rounded up to even)
-};
-
-RolloutGeom rollout_geom(int N, int64_t n) {
-  RolloutGeom g;
-  const int64_t nsteps = n - 1;
-  g.cw = pick_cw(nsteps);
-  g.passes = (int)((nsteps + 64 * g.cw - 1) / (64 * g.cw));
-  g.kc = (N + g.cw - 1) / g.cw * g.cw;           // k loop bound (k zero-padded)
-  g.lz = g.passes * 64 * g.cw + g.kc + 1;         // z_ref samples staged (padded with last)
-  g.kfm = 0;
-  if (g.cw & 1) {
-    // the fast-FIR form (odd CW) reads up to sample 64·CW + 2·kfm + W of the walk
-    const int U = g.cw / 2 + 1, mm = (N + 2) / 2;
-    g.kfm = (mm + U - 1) / U * U;
-    g.lz = std::max(g.lz, g.passes * 64 * g.cw + 2 * g.kfm + 2 * U + 2);
-  }
-  const int pad = (g.cw % 2 == 0) ? 1 : 0;
-  g.lzp = g.lz + pad * (g.lz / g.cw) + 1;         // LDS doubles per axis
-  // the z_ref area doubles as the history staging buffer: at least a third of a walk of rows
-  const int64_t stage_min = ((n + 2) / 3 * 6 + 1) / 2;
-  if (g.lzp < stage_min) g.lzp = (int)stage_min;
-  g.lzp = (g.lzp + 1) & ~1;
-  g.nf = g.passes == 1 ? 0 : (int)((nsteps + 2) & ~1LL);  // f lives in LDS only if passes > 1
-  g.kcp = (g.kc + 1) & ~1;
-  return g;
-}
-
-size_t lds_bytes(const RolloutGeom& g) {
-  return (size_t)(g.kcp + 2 * g.lzp + 2 * g.nf) * sizeof(double);
-}
 
 struct RolloutArgs {
   int kc, kcp, lz, lzp, n;
@@ -1117,8 +1067,8 @@ __device__ __forceinline__ void fft_correlate8(double2 (&v)[8], double2* buf,
 // changes go to an LDS list first (per-wave counts → prefix → positions, deterministic order)
 // and every lane walks its axis's list.  Returns false, uniformly over the workgroup, when
 // either axis has more than kSparseMaxWide changes (both axes then take the dense form: the FFT
-// correlates them together).  Both calls' barriers are reached by every thread.
-constexpr int kSparseMaxWide = 64;
+// correlates them together; kSparseMaxWide is in dispatch.h).  Both calls' barriers are reached by
+// every thread.
 
 template <int CW, int W>
 __device__ __forceinline__ bool wide_correlate_sparse(const RolloutArgs& a, const double* zr,
@@ -1174,12 +1124,6 @@ __device__ __forceinline__ bool wide_correlate_sparse(const RolloutArgs& a, cons
     for (int r = 0; r < CW; ++r) f[r] = fma(p[CW - 1 - r], dv, f[r]);
   }
   return true;
-}
-
-// LDS doubles the wide kernel's sparse attempt adds behind the two z_ref areas: the suffix-sum
-// table, the two change lists (values, then int positions)
-__host__ __device__ constexpr int wide_sparse_doubles(int N) {
-  return ((ksum_rows(N) + 1) & ~1) + 2 * kSparseMaxWide + kSparseMaxWide;
 }
 
 // Long walks (64·8+1 < n ≤ 64·8·8+1): the split-axis structure widened to W waves per axis
@@ -1495,37 +1439,6 @@ __global__ void __launch_bounds__(128 * W, E == 4 ? 6 : 4) zmpc_rollout_unc_wide
   if (a.dbg < 0) a.hist[tid] = pf0 + pf1;  // never (dbg ≥ 0): keeps the prefetch loads
 }
 
-// Geometry of the wide kernel: W waves per axis (2, 4 or 8), CW = ceil((n−1)/(64·W)) ≤ 8.
-struct WideGeom {
-  int w, cw, kc, lz, lzp;
-};
-
-#ifndef ZMPC_WIDE8  // (A/B builds only)
-#define ZMPC_WIDE8 0
-#endif
-constexpr bool kWide8 = ZMPC_WIDE8 != 0;
-
-// The wide kernel's dynamic-LDS ceiling: 64 KiB (the 4-waves-per-SIMD bound leaves no room above
-// it for W = 2 and 4), but 159 KiB for W = 8 — a 16-wave workgroup fills a CU's wave slots at that
-// bound alone, so its LDS costs no occupancy (walks of 2561..4096 samples at N >= 920 took the
-// chunk kernel at 8x the time, profiles/r6fin/configs/sweep_full.jsonl).  The kernel's static LDS
-// (≈0.5 KiB) comes on top: hipFuncSetAttribute refuses a dynamic limit of the full 160 KiB.
-size_t wide_lds_cap(int w) { return (size_t)(w == 8 ? 159 : 64) * 1024; }
-
-bool wide_geom(int N, int64_t n, WideGeom* g) {
-  const int64_t ns = n - 1;
-  // (449..512 timesteps: the single-pass split kernel's CW = 8 runs 1.7× slower per walk than
-  // its CW = 7, profiles/r4/r4hp_*; the wide kernel takes them at CW = 4 per wave pair)
-  if (ns <= 64 * 7 || ns > 64 * 8 * 8) return false;
-  g->w = ns <= 64 * 8 * 2 ? 2 : (ns <= 64 * 8 * 4 ? 4 : 8);
-  g->cw = (int)((ns + 64 * g->w - 1) / (64 * g->w));
-  g->kc = (N + g->cw - 1) / g->cw * g->cw;
-  g->lz = g->w * 64 * g->cw + g->kc + 1;
-  const int pad = (g->cw % 2 == 0) ? 1 : 0;
-  g->lzp = ((g->lz + pad * (g->lz / g->cw) + 1) + 1) & ~1;
-  return (size_t)2 * g->lzp * sizeof(double) <= wide_lds_cap(g->w);
-}
-
 // Walks of any length (the fallback beyond the wide kernel's 64·8·8 + 1 samples): one wave per
 // walk, the walk processed in chunks of `lc` timesteps with the two axes' states carried in
 // registers from chunk to chunk, so the LDS footprint does not grow with n.  Per chunk: the
@@ -1699,27 +1612,6 @@ __global__ void __launch_bounds__(64) zmpc_rollout_unc_chunk_kernel(RolloutArgs 
   }
 }
 
-// Chunk geometry: CW = 8, chunks of lc = 2·64·CW timesteps (two correlation passes), LDS =
-// k + z_ref (2 axes, lc + kc + 1 padded rows) + f (2 axes × lc): ≈ 45 KB at N = 512.
-struct ChunkGeom {
-  int lc, kc, kcp, lz, lzp;
-};
-
-ChunkGeom chunk_geom(int N) {
-  constexpr int CW = 8;
-  ChunkGeom g;
-  g.lc = 2 * 64 * CW;
-  g.kc = (N + CW - 1) / CW * CW;
-  g.kcp = (g.kc + CW + 1) & ~1;  // the correlation's sliding window reads one group past kc
-  g.lz = g.lc + g.kc + 1;
-  g.lzp = ((g.lz + g.lz / CW + 1) + 1) & ~1;
-  return g;
-}
-
-size_t chunk_lds_bytes(const ChunkGeom& g) {
-  return (size_t)(g.kcp + 2 * g.lzp + 2 * g.lc) * sizeof(double);
-}
-
 // Batched predict_wieber_axis (strict=False): one wave per instance.
 __global__ void __launch_bounds__(256) zmpc_step_unc_kernel(
     int64_t B, int N, LipmConsts lc, const double* __restrict__ k, const double* __restrict__ kxp,
@@ -1748,18 +1640,6 @@ __global__ void __launch_bounds__(256) zmpc_step_unc_kernel(
   }
 }
 
-// Any walk length: the chunked kernel (its own CW = 8 geometry).
-void launch_chunk(hipStream_t s, const RolloutArgs& a0, int N) {
-  const ChunkGeom g = chunk_geom(N);
-  RolloutArgs a = a0;
-  a.kc = g.kc;
-  a.kcp = g.kcp;
-  a.lz = g.lz;
-  a.lzp = g.lzp;
-  hipLaunchKernelGGL(zmpc_rollout_unc_chunk_kernel<8>, dim3((unsigned)a.B), dim3(64),
-                     chunk_lds_bytes(g), s, a, g.lc);
-}
-
 // Resident workgroups per CU of a kernel at an LDS size (a small per-host-thread cache keyed by
 // kernel, block size and LDS; every device of the pool is the same gfx950 part).
 int occupancy(const void* kernel, int threads, size_t lds) {
@@ -1781,101 +1661,75 @@ int occupancy(const void* kernel, int threads, size_t lds) {
   return occ;
 }
 
+// Which kernel a call takes, its geometry and its LDS are dispatch.h choose_unc's; the launchers
+// below pick the template instance of that choice and add the one rule that needs the runtime,
+// the next-dispatch-round prefetch (pf_ahead, from an occupancy query).
+
 // The wide kernel, with the next-dispatch-round prefetch when the batch takes at most two
 // rounds of resident workgroups (config 5 at ≈2.7 rounds: 64.4 vs 54.3 µs with it, so off there;
 // profiles/r3pfw/).
 template <int C, int W, int E>
-void launch_wide(hipStream_t s, RolloutArgs q, size_t lds, int64_t B, int cus) {
-  if (lds > 64 * 1024) {  // (W = 8 only, wide_lds_cap): raise the kernel's dynamic-LDS limit
-    static size_t raised = 64 * 1024;
-    if (lds > raised &&
-        hipFuncSetAttribute(reinterpret_cast<const void*>(zmpc_rollout_unc_wide_kernel<C, W, E>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) == hipSuccess)
-      raised = lds;
-  }
+void launch_wide(const UncChoice& c, hipStream_t s, RolloutArgs q, int cus) {
   const int occ = occupancy(reinterpret_cast<const void*>(zmpc_rollout_unc_wide_kernel<C, W, E>),
-                            128 * W, lds);
+                            128 * W, c.lds);
   const int64_t R = (int64_t)std::max(cus, 1) * occ;
-  q.pf_ahead = (R > 0 && q.n <= 512 * W && B <= 2 * R) ? R : 0;
-  hipLaunchKernelGGL((zmpc_rollout_unc_wide_kernel<C, W, E>), dim3((unsigned)B), dim3(128 * W),
-                     lds, s, q);
+  q.pf_ahead = (R > 0 && q.n <= 512 * W && q.B <= 2 * R) ? R : 0;
+  hipLaunchKernelGGL((zmpc_rollout_unc_wide_kernel<C, W, E>), dim3((unsigned)q.B), dim3(128 * W),
+                     c.lds, s, q);
 }
 
 // The wide kernel's instance for E points per thread.  E = 8 exists only where its transform
-// (P = 8·128·W points of 16 B) fits the 64 KiB LDS ceiling the launcher enforces, i.e. W ≤ 4:
+// (P = 8·128·W points of 16 B) fits the 64 KiB LDS ceiling choose_unc enforces, i.e. W ≤ 4:
 // an 8-wave E = 8 instance could never launch.
 template <int C, int W>
-void launch_wide_e(int E, hipStream_t s, const RolloutArgs& q, size_t lds, int64_t B, int cus) {
-  if (E == 4) {
-    launch_wide<C, W, 4>(s, q, lds, B, cus);
-    return;
-  }
+void launch_wide_e(const UncChoice& c, hipStream_t s, const RolloutArgs& q, int cus) {
+  if (c.E == 4) return launch_wide<C, W, 4>(c, s, q, cus);
   if constexpr (8 * 128 * W * 16 <= 64 * 1024) {
-    if (E == 8) {
-      launch_wide<C, W, 8>(s, q, lds, B, cus);
-      return;
-    }
+    if (c.E == 8) return launch_wide<C, W, 8>(c, s, q, cus);
   }
-  launch_wide<C, W, 0>(s, q, lds, B, cus);
+  launch_wide<C, W, 0>(c, s, q, cus);
 }
 
-// Walks of at most 64·8+1 samples (one correlation pass).  The split kernels (a 128-thread
-// workgroup per walk, one wave per axis) when their LDS fits the default 64 KiB ceiling:
-//   shared CoP (f precomputed): zmpc_rollout_unc_splitd_kernel<CW, true>;
-//   otherwise one walk per workgroup (odd CW: the fast-FIR dense form), with the next-round
-//     prefetch when the batch takes at most two dispatch rounds (config 2: 29.6 → 26.9 µs,
-//     profiles/r3pf/; with more rounds the touched lines are evicted before use, B = 16384:
-//     92 → 117 µs).  Round 4: even CW no longer take the persistent kernel (it has no prefetch;
-//     the horizon sweep's even-CW horizons were the slow ones, profiles/r4/); the diagnostics
-//     build keeps it behind ZMPC_PERSISTENT for A/B.
-// Otherwise (very long horizons) or with ZMPC_OPT_ROLLOUT_KERNEL = 1 (the cross-check):
-// zmpc_rollout_unc_kernel, one wave per walk.
+// Walks of at most 64·8+1 samples (one correlation pass): SplitShared, Generic or Split at tile
+// width CW.  Split runs with the next-round prefetch when the batch takes at most two dispatch
+// rounds (config 2: 29.6 → 26.9 µs, profiles/r3pf/; with more rounds the touched lines are
+// evicted before use, B = 16384: 92 → 117 µs).  Round 4: even CW no longer take the persistent
+// kernel (it has no prefetch; the horizon sweep's even-CW horizons were the slow ones,
+// profiles/r4/); the diagnostics build keeps it behind ZMPC_PERSISTENT for A/B.
 template <int CW>
-void launch_unc(const RolloutGeom& g, size_t lds, hipStream_t s, RolloutArgs a, int cus,
-                bool generic) {
-  const size_t lds_axis = lds - (size_t)a.kcp * sizeof(double);  // no staged gain row
-  size_t lds_split = std::max<size_t>(lds_axis, HistLayout<CW>::doubles(a.n) * sizeof(double));
-  // the sparse-difference correlation stages the plan's suffix sums behind the z_ref areas
-  const size_t lds_sparse = std::max(lds_axis + (size_t)ksum_rows(a.hN) * sizeof(double),
-                                     lds_split);
-  if (a.ksum != nullptr && lds_sparse <= 64 * 1024)
-    lds_split = lds_sparse;
-  else
-    a.ksum = nullptr;
-  if (a.fsh != nullptr) {
+void launch_unc(const UncChoice& c, hipStream_t s, RolloutArgs a, int cus) {
+  if (c.kind == UncKind::SplitShared) {
     // shared CoP, f precomputed: scan, replay and the history stores only
     hipLaunchKernelGGL((zmpc_rollout_unc_splitd_kernel<CW, true>), dim3((unsigned)a.B),
-                       dim3(128), HistLayout<CW>::doubles(a.n) * sizeof(double), s, a);
+                       dim3(128), c.lds, s, a);
     return;
   }
-  if (generic || lds_split > 64 * 1024) {
-    hipLaunchKernelGGL(zmpc_rollout_unc_kernel<CW>, dim3((unsigned)a.B), dim3(64), lds, s, a);
+  if (c.kind == UncKind::Generic) {
+    hipLaunchKernelGGL(zmpc_rollout_unc_kernel<CW>, dim3((unsigned)a.B), dim3(64), c.lds, s, a);
     return;
   }
 #ifdef ZMPC_DIAG
   static const bool pers = getenv("ZMPC_PERSISTENT") != nullptr;  // A/B: round-3 even-CW rule
   if ((CW & 1) == 0 && pers) {
     const int per_cu = occupancy(
-        reinterpret_cast<const void*>(zmpc_rollout_unc_persd_kernel<CW>), 128, lds_split);
+        reinterpret_cast<const void*>(zmpc_rollout_unc_persd_kernel<CW>), 128, c.lds);
     const int64_t grid = (int64_t)std::max(cus, 1) * per_cu;
     if (per_cu > 0 && grid < a.B && a.B <= 3 * grid) {
       hipLaunchKernelGGL(zmpc_rollout_unc_persd_kernel<CW>, dim3((unsigned)grid), dim3(128),
-                         lds_split, s, a);
+                         c.lds, s, a);
       return;
     }
   }
 #endif
   const int occ = occupancy(
-      reinterpret_cast<const void*>(zmpc_rollout_unc_splitd_kernel<CW, false>), 128, lds_split);
+      reinterpret_cast<const void*>(zmpc_rollout_unc_splitd_kernel<CW, false>), 128, c.lds);
   const int64_t R = (int64_t)std::max(cus, 1) * occ;
   a.pf_ahead = (R > 0 && a.n <= 512 && a.B <= 2 * R) ? R : 0;
   hipLaunchKernelGGL((zmpc_rollout_unc_splitd_kernel<CW, false>), dim3((unsigned)a.B),
-                     dim3(128), lds_split, s, a);
+                     dim3(128), c.lds, s, a);
 }
 
 }  // namespace
-
-size_t zmpc_rollout_unc_lds_bytes(int N, int64_t n) { return lds_bytes(rollout_geom(N, n)); }
 
 #ifdef ZMPC_DIAG
 // diagnostics: the phase stamps of the last launch to $ZMPC_ROLLOUT_TL ([B][5] u64)
@@ -1892,21 +1746,10 @@ static void tl_write(const unsigned long long* tl, int64_t B, hipStream_t s, hip
 }
 #endif
 
-hipError_t zmpc_launch_rollout_unc(const zmpc_plan* p, int64_t B, int64_t n, const double* zmax,
-                                   const double* zmin, int64_t bstride, const double* x0,
-                                   const double* kick, int64_t kick_step,
-                                   const int64_t* kick_steps, double* hist, int32_t* status,
-                                   hipStream_t s, std::string* why) {
-  if (n == 1) {
-    // no QP solve: the history is the initial state only
-    hipError_t e = hipMemcpyAsync(hist, x0, 6 * sizeof(double) * (size_t)B,
-                                  hipMemcpyDeviceToDevice, s);
-    if (e != hipSuccess) return e;
-    if (status) return hipMemsetAsync(status, 0, sizeof(int32_t) * B, s);
-    return hipSuccess;
-  }
-  const RolloutGeom g = rollout_geom(p->N, n);
-  const size_t lds = lds_bytes(g);
+hipError_t zmpc_launch_rollout_unc(const zmpc_plan* p, const RolloutCall& rc, hipStream_t s,
+                                   std::string* why) {
+  const UncChoice c = choose_unc(p->N, rc.n, rc.bstride == 0, p->opt[ZMPC_OPT_ROLLOUT_KERNEL],
+                                 p->opt[ZMPC_OPT_LONG_WALK], p->opt[ZMPC_OPT_CORRELATION]);
 #ifdef ZMPC_DIAG
   static const int dbg = [] {
     const char* e = getenv("ZMPC_DEBUG_ROLLOUT");  // diagnostics build: ablation bits
@@ -1916,135 +1759,108 @@ hipError_t zmpc_launch_rollout_unc(const zmpc_plan* p, int64_t B, int64_t n, con
   constexpr int dbg = 0;
 #endif
   RolloutArgs a{};
-  a.kc = g.kc;
-  a.kcp = g.kcp;
-  a.lz = g.lz;
-  a.lzp = g.lzp;
-  a.n = (int)n;
-  a.B = B;
+  a.kc = c.kc;
+  a.kcp = c.kcp;
+  a.lz = c.lz;
+  a.lzp = c.lzp;
+  a.n = (int)rc.n;
+  a.B = rc.B;
   a.lc = p->lc;
   a.k = p->k;
   a.kx = p->kx;
-  a.zmax = zmax;
-  a.zmin = zmin;
-  a.bstride = bstride;
-  a.x0 = x0;
-  a.kick = kick;
-  a.kick_step = kick_step;
-  a.hist = hist;
-  a.status = status;
+  a.zmax = rc.zmax;
+  a.zmin = rc.zmin;
+  a.bstride = rc.bstride;
+  a.x0 = rc.x0;
+  a.kick = rc.kick;
+  a.kick_step = rc.kick_step;
+  a.hist = rc.hist;
+  a.status = rc.status;
   a.scanP = p->scanP;
   a.dbg = dbg;
-  a.kick_steps = kick_steps;
+  a.kick_steps = rc.kick_steps;
   a.kffa = p->kffa;
-  a.kfm = g.kfm;
-  // ZMPC_OPT_CORRELATION = 1: the dense correlation forms only (cross-checks, and bench.py's
-  // dense-form timing beside the default)
-  a.ksum = p->opt[ZMPC_OPT_CORRELATION] == 1 ? nullptr : p->ksum;
+  a.kfm = c.kfm;
+  a.ksum = c.sparse ? p->ksum : nullptr;
   a.hN = p->N;
+  a.fstride = c.fstride;
+  if (c.E) {
+    a.fft_tw = reinterpret_cast<const double2*>(p->fft_tw);
+    a.fft_g = reinterpret_cast<const double2*>(p->fft_g) + (c.P - kFftPmin);
+  }
 #ifdef ZMPC_DIAG
   // diagnostics: per-walk phase stamps of the split and wide kernels, written to $ZMPC_ROLLOUT_TL after
   // every launch ([B][5] u64, wall_clock64 ticks)
   static unsigned long long* tl_buf = nullptr;
   static int64_t tl_cap = 0;
-  if (getenv("ZMPC_ROLLOUT_TL") && B > tl_cap) {
+  if (getenv("ZMPC_ROLLOUT_TL") && rc.B > tl_cap) {
     if (tl_buf) (void)hipFree(tl_buf);
     tl_buf = nullptr;
-    tl_cap = hipMalloc((void**)&tl_buf, (size_t)B * 5 * 8) == hipSuccess ? B : 0;
+    tl_cap = hipMalloc((void**)&tl_buf, (size_t)rc.B * 5 * 8) == hipSuccess ? rc.B : 0;
   }
-  if (tl_buf) {
-    (void)hipMemsetAsync(tl_buf, 0, (size_t)B * 5 * 8, s);
+  if (tl_buf && c.kind != UncKind::Copy && c.kind != UncKind::Chunk) {
+    (void)hipMemsetAsync(tl_buf, 0, (size_t)rc.B * 5 * 8, s);
     a.tl = tl_buf;
   }
 #endif
-  const int long_form = p->opt[ZMPC_OPT_LONG_WALK];  // 0 auto, 1 direct, 2 FFT, 3 chunk kernel
-  WideGeom wg;
-  if (g.passes > 1 && (long_form == 3 || !wide_geom(p->N, n, &wg))) {
-    launch_chunk(s, a, p->N);  // any length (the whole walk does not fit one pass)
-    return hipGetLastError();
-  }
-  if (lds > 160 * 1024) {  // single-pass geometry beyond LDS (very long horizon N)
-    launch_chunk(s, a, p->N);
-    return hipGetLastError();
-  }
-  const bool generic = p->opt[ZMPC_OPT_ROLLOUT_KERNEL] == 1;
-  // per-walk bounds whose single pass would run at CW = 8 take the wide kernel (wide_geom)
-  const bool wide8 = kWide8 && g.passes == 1 && g.cw == 8 && bstride != 0 && !generic &&
-                     wide_geom(p->N, n, &wg);
-  if (g.passes > 1 || wide8) {
-    RolloutArgs q = a;
-    q.kc = wg.kc;
-    q.lz = wg.lz;
-    q.lzp = wg.lzp;
-    size_t lds_w = 2 * (size_t)wg.lzp * sizeof(double);
-    // FFT correlation when the transform maps onto the workgroup (E = P/NT points per thread,
-    // 4 or 8), fits the default LDS ceiling and costs less than the direct form: measured
-    // crossover (n − 1)·N ≥ 9·P·log2 P — N = 150 walks of 1000/2000 samples
-    // are faster direct, N ≥ 200 faster by FFT.  ZMPC_OPT_LONG_WALK 1 / 2 forces the direct
-    // form / the FFT wherever it fits.
-    int P = kFftPmin;
-    while (P < n - 1 + p->N) P *= 2;
-    const int NT = 128 * wg.w;
-    int E = (P % NT == 0) ? P / NT : 0;
-    if (long_form == 1 || (E != 4 && E != 8) || P > kFftPT || (size_t)P * 16 > 64 * 1024) E = 0;
-    if (long_form == 0 && (double)(n - 1) * p->N < 9.0 * P * __builtin_ctz((unsigned)P)) E = 0;
-    if (E) {
-      q.fft_tw = reinterpret_cast<const double2*>(p->fft_tw);
-      q.fft_g = reinterpret_cast<const double2*>(p->fft_g) + (P - kFftPmin);
-      lds_w = std::max(lds_w, (size_t)P * 16);
+  double* fsh = nullptr;  // SplitShared: f of the shared CoP, once per launch
+  switch (c.kind) {
+    case UncKind::Copy: {
+      // no QP solve: the history is the initial state only
+      hipError_t e = hipMemcpyAsync(rc.hist, rc.x0, 6 * sizeof(double) * (size_t)rc.B,
+                                    hipMemcpyDeviceToDevice, s);
+      if (e != hipSuccess) return e;
+      if (rc.status) return hipMemsetAsync(rc.status, 0, sizeof(int32_t) * rc.B, s);
+      return hipSuccess;
     }
-    // the sparse attempt's table and change lists behind the z_ref areas (within the default
-    // 64 KiB dynamic-LDS ceiling, else dense only)
-    const size_t lds_sp = (2 * (size_t)wg.lzp + wide_sparse_doubles(p->N)) * sizeof(double);
-    if (q.ksum != nullptr && lds_sp <= wide_lds_cap(wg.w))
-      lds_w = std::max(lds_w, lds_sp);
-    else
-      q.ksum = nullptr;
-    switch (wg.w * 16 + wg.cw) {
-#define ZMPC_WCASE(W, C)                                \
-  case W * 16 + C:                                      \
-    launch_wide_e<C, W>(E, s, q, lds_w, B, p->cus);     \
+    case UncKind::Chunk:
+      hipLaunchKernelGGL(zmpc_rollout_unc_chunk_kernel<8>, dim3((unsigned)a.B), dim3(64), c.lds,
+                         s, a, c.lc);
+      break;
+    case UncKind::Wide:
+      // (the twelve shapes choose_unc can return: W = 2, 4, 8 at CW = 5..8)
+      switch (c.w * 16 + c.cw) {
+#define ZMPC_WCASE(W, C)                     \
+  case W * 16 + C:                           \
+    launch_wide_e<C, W>(c, s, a, p->cus);    \
     break;
-      ZMPC_WCASE(2, 4) ZMPC_WCASE(2, 5) ZMPC_WCASE(2, 6) ZMPC_WCASE(2, 7) ZMPC_WCASE(2, 8)
-      ZMPC_WCASE(4, 5) ZMPC_WCASE(4, 6) ZMPC_WCASE(4, 7) ZMPC_WCASE(4, 8)
-      ZMPC_WCASE(8, 5) ZMPC_WCASE(8, 6) ZMPC_WCASE(8, 7) ZMPC_WCASE(8, 8)
+        ZMPC_WCASE(2, 5) ZMPC_WCASE(2, 6) ZMPC_WCASE(2, 7) ZMPC_WCASE(2, 8)
+        ZMPC_WCASE(4, 5) ZMPC_WCASE(4, 6) ZMPC_WCASE(4, 7) ZMPC_WCASE(4, 8)
+        ZMPC_WCASE(8, 5) ZMPC_WCASE(8, 6) ZMPC_WCASE(8, 7) ZMPC_WCASE(8, 8)
 #undef ZMPC_WCASE
-      default:
-        return hipErrorInvalidValue;
+        default:
+          return hipErrorInvalidValue;
+      }
+      break;
+    case UncKind::SplitShared: {
+      const hipError_t e = hipMallocAsync((void**)&fsh, 2 * (size_t)c.fstride * sizeof(double), s);
+      if (e != hipSuccess) {
+        (void)hipGetLastError();
+        return hipErrorOutOfMemory;
+      }
+      hipLaunchKernelGGL(zmpc_shared_f_kernel, dim3((unsigned)((c.fstride + 255) / 256), 2),
+                         dim3(256), 0, s, rc.zmax, rc.zmin, (int)rc.n, p->k, c.kc, fsh, c.fstride);
+      a.fsh = fsh;
     }
-    const hipError_t ew = hipGetLastError();
-#ifdef ZMPC_DIAG
-    tl_write(a.tl, B, s, ew);
-#endif
-    return ew;
-  }
-  // shared CoP (bounds stride 0) with a single-pass geometry: f once per launch
-  double* fsh = nullptr;
-  if (bstride == 0 && !generic && (6 * (size_t)n + 2 * (size_t)n) * sizeof(double) <= 64 * 1024) {
-    a.fstride = ((64 * g.cw) + 63) & ~63;  // every lane's CW values, padded
-    hipError_t e = hipMallocAsync((void**)&fsh, 2 * (size_t)a.fstride * sizeof(double), s);
-    if (e != hipSuccess) {
-      (void)hipGetLastError();
-      return hipErrorOutOfMemory;
-    }
-    hipLaunchKernelGGL(zmpc_shared_f_kernel, dim3((unsigned)((a.fstride + 255) / 256), 2),
-                       dim3(256), 0, s, zmax, zmin, (int)n, p->k, g.kc, fsh, a.fstride);
-    a.fsh = fsh;
-  }
-  switch (g.cw) {
-#define ZMPC_CW(C)                                   \
-  case C:                                            \
-    launch_unc<C>(g, lds, s, a, p->cus, generic);    \
+      [[fallthrough]];
+    case UncKind::Split:
+    case UncKind::Generic:
+      switch (c.cw) {
+#define ZMPC_CW(C)                      \
+  case C:                               \
+    launch_unc<C>(c, s, a, p->cus);     \
     break;
-    ZMPC_CW(1) ZMPC_CW(2) ZMPC_CW(3) ZMPC_CW(4) ZMPC_CW(5) ZMPC_CW(6) ZMPC_CW(7) ZMPC_CW(8)
+        ZMPC_CW(1) ZMPC_CW(2) ZMPC_CW(3) ZMPC_CW(4) ZMPC_CW(5) ZMPC_CW(6) ZMPC_CW(7) ZMPC_CW(8)
 #undef ZMPC_CW
-    default:
-      if (fsh) (void)hipFreeAsync(fsh, s);
-      return hipErrorInvalidValue;
+        default:
+          if (fsh) (void)hipFreeAsync(fsh, s);
+          return hipErrorInvalidValue;
+      }
+      break;
   }
   hipError_t e = hipGetLastError();
 #ifdef ZMPC_DIAG
-  tl_write(a.tl, B, s, e);
+  tl_write(a.tl, rc.B, s, e);
 #endif
   if (fsh) {
     const hipError_t ef = hipFreeAsync(fsh, s);
@@ -2053,11 +1869,9 @@ hipError_t zmpc_launch_rollout_unc(const zmpc_plan* p, int64_t B, int64_t n, con
   return e;
 }
 
-hipError_t zmpc_launch_step_unc(const zmpc_plan* p, int64_t B, const double* x,
-                                const double* zmax_win, const double* zmin_win, double* x_next,
-                                int32_t* status, hipStream_t s) {
-  hipLaunchKernelGGL(zmpc_step_unc_kernel, dim3((unsigned)((B + 3) / 4)), dim3(256), 0, s, B,
-                     p->N, p->lc, p->k, p->kx, x, zmax_win, zmin_win, x_next, status);
+hipError_t zmpc_launch_step_unc(const zmpc_plan* p, const StepCall& c, hipStream_t s) {
+  hipLaunchKernelGGL(zmpc_step_unc_kernel, dim3((unsigned)((c.B + 3) / 4)), dim3(256), 0, s, c.B,
+                     p->N, p->lc, p->k, p->kx, c.x, c.zmax_win, c.zmin_win, c.x_next, c.status);
   return hipGetLastError();
 }
 
@@ -2075,5 +1889,14 @@ hipError_t zmpc_rollout_unc_set_attrs() {
   if (e == hipSuccess)
     e = hipFuncSetAttribute((const void*)zmpc_rollout_unc_chunk_kernel<8>,
                             hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+  // the 8-wave wide kernel runs up to wide_lds_cap(8): its instances are CW = 5..8 with E = 0 or 4
+  // (launch_wide_e: E = 8 has no 8-wave instance)
+#define ZMPC_WATTR(C, E)                                                                      \
+  if (e == hipSuccess)                                                                        \
+    e = hipFuncSetAttribute((const void*)zmpc_rollout_unc_wide_kernel<C, 8, E>,              \
+                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)wide_lds_cap(8));
+  ZMPC_WATTR(5, 0) ZMPC_WATTR(6, 0) ZMPC_WATTR(7, 0) ZMPC_WATTR(8, 0)
+  ZMPC_WATTR(5, 4) ZMPC_WATTR(6, 4) ZMPC_WATTR(7, 4) ZMPC_WATTR(8, 4)
+#undef ZMPC_WATTR
   return e;
 }

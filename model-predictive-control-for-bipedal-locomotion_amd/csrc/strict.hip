@@ -943,7 +943,7 @@ hipError_t zmpc_strict_set_attrs() {
 
 static hipError_t launch_strict(const zmpc_plan* p, StrictArgs a, hipStream_t s,
                                 std::string* why) {
-  if (p->N > 512) {
+  if (p->N > kStrictCholMaxN) {
     *why = "strict solver supports horizon N <= 512";
     return hipErrorInvalidValue;
   }
@@ -1040,38 +1040,9 @@ static hipError_t launch_strict(const zmpc_plan* p, StrictArgs a, hipStream_t s,
   return e;
 }
 
-// The strict solver of a launch over `ninst` instances (ZMPC_OPT_STRICT_SOLVER: 1 the tile
-// kernel above, 2 the reduced-Cholesky one-instance-per-wave kernel, 3 the LQ lane-per-instance
-// kernel of strict_lq.hip, 4 the parallel-in-time one-instance-per-wave kernel of
-// strict_scan.hip, 0 = auto): small batches take the parallel-in-time kernel and large ones the
-// LQ kernel, whose per-pass work is O(N) per lane but serial within it.  The reduced-Cholesky
-// wave kernel is a cross-check (profiles/r4/r4e_strict_small_batch.jsonl, N = 150, n = 420: 1
-// walk 27.6 ms vs the LQ kernel's 29.0, 8 walks 92.8 vs 46.4 — its passes are long when a
-// kicked walk pins many slots).
-// Option 4 / auto at up to kScanMaxInst instances: the parallel-in-time kernel of
-// strict_scan.hip (one instance per wave, the horizon over the lanes).  Crossover measured at
-// N = 150, n = 420 (profiles/r4/r4h_crossover.jsonl): 4096 walks 19.9 vs 55.2 ms (LQ), 8192
-// walks 35.6 vs 56.8, 16384 walks 65.2 vs 57.8 — the LQ kernel won from ≈14 000 walks.  Round 5
-// (profiles/r5r/cross.jsonl; both kernels faster): 8192 walks 45.0 vs 47.0 ms, 12288 walks 64.9
-// vs 47.6 — the LQ kernel wins from ≈8 600 walks.
-constexpr int64_t kScanMaxInst = 16384;
-enum { kTile = 1, kWave = 2, kLq = 3, kScan = 4 };
-
-static int strict_mode(const zmpc_plan* p, int64_t ninst) {
-  const int opt = p->opt[ZMPC_OPT_STRICT_SOLVER];
-  const bool lq_ok = zmpc_strict_lq_supported(p);
-  const bool scan_ok = zmpc_strict_scan_supported(p);
-  if (opt == 1) return kTile;
-  if (opt == 2) return kWave;
-  if (opt == 3) return kLq;    // (zmpc_plan_set_option accepts 3 and 4 only where they run)
-  if (opt == 4) return kScan;
-  if (scan_ok && (ninst <= kScanMaxInst || !lq_ok)) return kScan;
-  return lq_ok ? kLq : kTile;
-}
-
 static hipError_t launch_strict_wave(const zmpc_plan* p, StrictArgs a, hipStream_t s,
                                      std::string* why) {
-  if (p->N > 512) {
+  if (p->N > kStrictCholMaxN) {
     *why = "strict solver supports horizon N <= 512";
     return hipErrorInvalidValue;
   }
@@ -1129,58 +1100,44 @@ static hipError_t launch_strict_wave(const zmpc_plan* p, StrictArgs a, hipStream
   return e != hipSuccess ? e : ef;
 }
 
-hipError_t zmpc_launch_rollout_strict(const zmpc_plan* p, int64_t B, int64_t n,
-                                      const double* zmax, const double* zmin, int64_t bstride,
-                                      const double* x0, const double* kick, int64_t kick_step,
-                                      const int64_t* kick_steps, double* hist, int32_t* status,
-                                      hipStream_t s, std::string* why) {
-  const int mode = strict_mode(p, 2 * B);
-  if (mode == kScan && n > 1)
-    return zmpc_launch_rollout_strict_scan(p, B, n, zmax, zmin, bstride, x0, kick, kick_step,
-                                           kick_steps, hist, status, s, why);
-  if (mode == kLq && n > 1)
-    return zmpc_launch_rollout_strict_lq(p, B, n, zmax, zmin, bstride, x0, kick, kick_step,
-                                         kick_steps, hist, status, s, why);
+// WAVE: the one-instance-per-wave kernel, else the tile kernel
+template <bool WAVE>
+static hipError_t rollout_chol(const zmpc_plan* p, const RolloutCall& c, hipStream_t s,
+                               std::string* why) {
   if (!p->G) {
     *why = "plan was created without strict workspace";
     return hipErrorInvalidValue;
   }
-  if (n == 1) {
-    hipError_t e = hipMemcpyAsync(hist, x0, 6 * sizeof(double) * (size_t)B,
+  if (c.n == 1) {
+    hipError_t e = hipMemcpyAsync(c.hist, c.x0, 6 * sizeof(double) * (size_t)c.B,
                                   hipMemcpyDeviceToDevice, s);
     if (e != hipSuccess) return e;
-    if (status) return hipMemsetAsync(status, 0, sizeof(int32_t) * B, s);
+    if (c.status) return hipMemsetAsync(c.status, 0, sizeof(int32_t) * c.B, s);
     return hipSuccess;
   }
-  if (status) {
-    hipError_t e = hipMemsetAsync(status, 0, sizeof(int32_t) * B, s);
+  if (c.status) {
+    hipError_t e = hipMemsetAsync(c.status, 0, sizeof(int32_t) * c.B, s);
     if (e != hipSuccess) return e;
   }
   StrictArgs a{};
   a.window_mode = 0;
-  a.n = n;
-  a.bstride = bstride;
-  a.ninst = 2 * B;
-  a.zmax = zmax;
-  a.zmin = zmin;
-  a.x0 = x0;
-  a.kick = kick;
-  a.kick_step = kick_step;
-  a.kick_steps = kick_steps;
-  a.out = hist;
-  a.status = status;
-  return mode == kWave ? launch_strict_wave(p, a, s, why) : launch_strict(p, a, s, why);
+  a.n = c.n;
+  a.bstride = c.bstride;
+  a.ninst = 2 * c.B;
+  a.zmax = c.zmax;
+  a.zmin = c.zmin;
+  a.x0 = c.x0;
+  a.kick = c.kick;
+  a.kick_step = c.kick_step;
+  a.kick_steps = c.kick_steps;
+  a.out = c.hist;
+  a.status = c.status;
+  return WAVE ? launch_strict_wave(p, a, s, why) : launch_strict(p, a, s, why);
 }
 
-hipError_t zmpc_launch_step_strict(const zmpc_plan* p, int64_t B, const double* x,
-                                   const double* zmax_win, const double* zmin_win,
-                                   double* x_next, int32_t* status, hipStream_t s,
-                                   std::string* why) {
-  const int mode = strict_mode(p, B);
-  if (mode == kScan)
-    return zmpc_launch_step_strict_scan(p, B, x, zmax_win, zmin_win, x_next, status, s, why);
-  if (mode == kLq)
-    return zmpc_launch_step_strict_lq(p, B, x, zmax_win, zmin_win, x_next, status, s, why);
+template <bool WAVE>
+static hipError_t step_chol(const zmpc_plan* p, const StepCall& c, hipStream_t s,
+                            std::string* why) {
   if (!p->G) {
     *why = "plan was created without strict workspace";
     return hipErrorInvalidValue;
@@ -1188,13 +1145,33 @@ hipError_t zmpc_launch_step_strict(const zmpc_plan* p, int64_t B, const double* 
   StrictArgs a{};
   a.window_mode = 1;
   a.n = 0;
-  a.ninst = B;
-  a.zmax = zmax_win;
-  a.zmin = zmin_win;
-  a.x0 = x;
+  a.ninst = c.B;
+  a.zmax = c.zmax_win;
+  a.zmin = c.zmin_win;
+  a.x0 = c.x;
   a.kick = nullptr;
   a.kick_step = -1;
-  a.out = x_next;
-  a.status = status;
-  return mode == kWave ? launch_strict_wave(p, a, s, why) : launch_strict(p, a, s, why);
+  a.out = c.x_next;
+  a.status = c.status;
+  return WAVE ? launch_strict_wave(p, a, s, why) : launch_strict(p, a, s, why);
+}
+
+hipError_t zmpc_launch_rollout_strict_tile(const zmpc_plan* p, const RolloutCall& c,
+                                           hipStream_t s, std::string* why) {
+  return rollout_chol<false>(p, c, s, why);
+}
+
+hipError_t zmpc_launch_step_strict_tile(const zmpc_plan* p, const StepCall& c, hipStream_t s,
+                                        std::string* why) {
+  return step_chol<false>(p, c, s, why);
+}
+
+hipError_t zmpc_launch_rollout_strict_wave(const zmpc_plan* p, const RolloutCall& c,
+                                           hipStream_t s, std::string* why) {
+  return rollout_chol<true>(p, c, s, why);
+}
+
+hipError_t zmpc_launch_step_strict_wave(const zmpc_plan* p, const StepCall& c, hipStream_t s,
+                                        std::string* why) {
+  return step_chol<true>(p, c, s, why);
 }

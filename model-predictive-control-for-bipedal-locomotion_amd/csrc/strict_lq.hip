@@ -74,12 +74,14 @@ constexpr bool kLqProf = false;
 // Riccati steps per checkpoint segment.  Fixed at 8: a segment's working-set flags are one
 // 16-bit LDS word (Flags: [slot / 8][64], 2 bits per slot), which the segment loads, the
 // new-flag writes and the warm-start shift all take whole (rounds 1-3 measured S = 6/10/12/16:
-// slower or spilling).
-constexpr int LQ_S = 8;
+// slower or spilling).  (LQ_S = 8 and kLdsCk, the LDS checkpoints per wave, are in dispatch.h:
+// they size the workgroup's LDS, lq_shape.  The host emulation of this kernel source, tests/emu,
+// names kLdsCk and lq_lds_bytes as members of this namespace, so they are declared into it.)
+using ::kLdsCk;
+using ::lq_lds_bytes;
 constexpr int LQ_DRIFT = ZMPC_LQ_DRIFT;  // timesteps a lane may run ahead of its wave's slowest lane
                               // (round 3, profiles/r3u/, r3drift/: 0/1/2/4/8 → 104.5/94.8/92.5/
                               // 90.9/92.7 ms at config 3 — the bound rows stay a few rows apart)
-constexpr int kLdsCk = 2;  // at most this many LDS checkpoints per wave (LqArgs::nlck)
 constexpr int TAB = 16;       // doubles per slot of the free-tail table: [0..2] K, [3] 1/Quu,
                               // [4..9] P after the slot (V_k: slots k..N−1 free), [10..12] Qux,
                               // padding
@@ -361,8 +363,7 @@ struct Flags {
   }
 };
 
-// 32-bit flag words of a wave (two segments each)
-__host__ __device__ constexpr int flag_dwords(int NS) { return (NS + 1) / 2; }
+// (32-bit flag words of a wave, two segments each: dispatch.h flag_dwords)
 
 // A value function parked in the wave's LDS slot ([9][64] doubles).
 __device__ __forceinline__ void park(double* vp, const Ric& v, int lane) {
@@ -1267,29 +1268,11 @@ const LqVariant kLqVariants[] = {
 };
 #undef ZMPC_LQV
 #undef ZMPC_LQK
-constexpr size_t kLdsCap = 160 * 1024;
 
-// LDS of one workgroup: the G waves' slot flags (2 bits per slot and lane), parked V and state
-// ([12][64] doubles each) and nlck LDS checkpoints ([9][64] doubles each).
-constexpr size_t lq_lds_bytes(int G, int N, int nlck = 0) {
-  const size_t segs = (size_t)(N + LQ_S - 1) / LQ_S;
-  return (size_t)G * ((size_t)flag_dwords((int)segs) * 64 * 4 +
-                      (12 + 9 * (size_t)nlck) * 64 * sizeof(double));
-}
-
-// LDS checkpoints per wave that fit beside a workgroup shape (config 3, N = 150: 2 at G = 8)
-int lq_nlck_for(int G, int N) {
-  int c = kLdsCk;
-  while (c > 0 && lq_lds_bytes(G, N, c) > 160 * 1024) --c;
-  return c;
-}
-
-static_assert(lq_lds_bytes(2, ZMPC_STRICT_MAX_N) <= kLdsCap, "ZMPC_STRICT_MAX_N past the LDS");
-
-// The largest workgroup whose slot flags and parks fit a CU (N ≤ 2464 at G = 2).
-const LqVariant* lq_variant_for(int N) {
+// The kernels of a workgroup shape (dispatch.h lq_shape: G = 8, 4 or 2).
+const LqVariant* lq_variant(int G) {
   for (const LqVariant& c : kLqVariants)
-    if (lq_lds_bytes(c.G, N) <= kLdsCap) return &c;
+    if (c.G == G) return &c;
   return nullptr;
 }
 
@@ -1304,14 +1287,18 @@ void fill_consts(const zmpc_plan* p, LqArgs& a) {
 }
 
 hipError_t launch_lq(const zmpc_plan* p, LqArgs& a, int64_t waves, hipStream_t s) {
-  const LqVariant* var = lq_variant_for(p->N);
+  const LqShape shape = lq_shape(p->N);
+  const LqVariant* var = lq_variant(shape.G);
   if (!var) return hipErrorInvalidValue;
   const int64_t blocks = (waves + var->G - 1) / var->G;
-  a.nlck = lq_nlck_for(var->G, p->N);
+  a.nlck = shape.nlck;
+  size_t lds = shape.lds;
 #ifdef ZMPC_DIAG
-  if (const char* e = getenv("ZMPC_LQ_NLCK")) a.nlck = std::min(a.nlck, atoi(e));  // (A/B)
+  if (const char* e = getenv("ZMPC_LQ_NLCK")) {  // (A/B)
+    a.nlck = std::min(a.nlck, atoi(e));
+    lds = lq_lds_bytes(var->G, p->N, a.nlck);
+  }
 #endif
-  const size_t lds = lq_lds_bytes(var->G, p->N, a.nlck);
   // cached checkpoints (see CkIO: with run-length bounds the window rows no longer compete
   // for the caches, and non-temporal checkpoints became the slower form — config 3 55.4 vs
   // 56.7 ms, diagnostics build, profiles/r5m/)
@@ -1397,8 +1384,7 @@ hipError_t zmpc_strict_lq_set_attrs() {
 }
 
 bool zmpc_strict_lq_supported(const zmpc_plan* p) {
-  return p->N >= 1 && p->N <= ZMPC_STRICT_MAX_N && p->lqtab != nullptr &&
-         lq_variant_for(p->N) != nullptr;
+  return strict_lq_supported(p->N, p->lqtab != nullptr);
 }
 
 size_t zmpc_strict_lq_table_doubles(int N) { return (size_t)N * TAB; }
@@ -1410,12 +1396,9 @@ hipError_t zmpc_strict_lq_build_table(zmpc_plan* p, hipStream_t s) {
   return hipGetLastError();
 }
 
-hipError_t zmpc_launch_rollout_strict_lq(const zmpc_plan* p, int64_t B, int64_t n,
-                                         const double* zmax, const double* zmin,
-                                         int64_t bstride, const double* x0, const double* kick,
-                                         int64_t kick_step, const int64_t* kick_steps,
-                                         double* hist, int32_t* status, hipStream_t s,
+hipError_t zmpc_launch_rollout_strict_lq(const zmpc_plan* p, const RolloutCall& c, hipStream_t s,
                                          std::string* why) {
+  const int64_t B = c.B, n = c.n;
   LqArgs a{};
   fill_consts(p, a);
   a.window_mode = 0;
@@ -1423,23 +1406,23 @@ hipError_t zmpc_launch_rollout_strict_lq(const zmpc_plan* p, int64_t B, int64_t 
   a.n = n;
   a.nsteps = n - 1;
   a.B = B;
-  a.x0 = x0;
-  a.kick = kick;
-  a.kick_step = kick_step;
-  a.kick_steps = kick_steps;
-  a.out = hist;
-  a.status = status;
+  a.x0 = c.x0;
+  a.kick = c.kick;
+  a.kick_step = c.kick_step;
+  a.kick_steps = c.kick_steps;
+  a.out = c.hist;
+  a.status = c.status;
   hipError_t e = hipSuccess;
-  if (status && (e = hipMemsetAsync(status, 0, sizeof(int32_t) * B, s)) != hipSuccess) return e;
+  if (c.status && (e = hipMemsetAsync(c.status, 0, sizeof(int32_t) * B, s)) != hipSuccess)
+    return e;
   const int64_t waves = 2 * ((B + 63) / 64);
   // workspace: checkpoints + the staged bounds (rows past n − 1: the padded windows)
-  a.shared = bstride == 0 ? 1 : 0;
+  a.shared = c.bstride == 0 ? 1 : 0;
   const int64_t Bst = a.shared ? 64 : B;  // a shared CoP is staged once, 64 identical lanes
   a.groups = (Bst + 63) / 64;
   a.rows = n + (int64_t)a.NS * LQ_S;  // the last segment reads up to NS·S − 1 ahead
-  const LqVariant* var = lq_variant_for(p->N);
-  if (!var) return hipErrorInvalidValue;
-  const int64_t G = var->G;  // checkpoints for every wave of the launched blocks
+  const int64_t G = lq_shape(p->N).G;  // checkpoints for every wave of the launched blocks
+  if (G == 0) return hipErrorInvalidValue;
   const size_t ck_doubles = (size_t)((waves + G - 1) / G * G) * a.NS * kCkStride;
   // bounds: rows (2 axes × rows × 64 (z_ref, half-width)) or runs (per (axis, group) up to
   // n + 2 runs of a pair and a start time).  ZMPC_OPT_STRICT_BOUNDS 0 (auto) = runs
@@ -1454,7 +1437,7 @@ hipError_t zmpc_launch_rollout_strict_lq(const zmpc_plan* p, int64_t B, int64_t 
                                  : (size_t)2 * a.groups * a.rows * 64 * 2;
   // kick order (order.hip): walks with per-walk kicks sorted by (kick step, kick) onto lanes,
   // when there is more than one wave of them (ZMPC_OPT_KICK_ORDER = 0 keeps the input order)
-  const bool ordered = p->opt[ZMPC_OPT_KICK_ORDER] != 0 && kick != nullptr && B > 64;
+  const bool ordered = p->opt[ZMPC_OPT_KICK_ORDER] != 0 && c.kick != nullptr && B > 64;
   const size_t perm_doubles = ordered ? ((size_t)B * 4 + 7) / 8 : 0;
   const size_t ord_doubles = ordered ? (zmpc_kick_order_bytes(B) + 7) / 8 : 0;
   double* ws = nullptr;
@@ -1470,7 +1453,7 @@ hipError_t zmpc_launch_rollout_strict_lq(const zmpc_plan* p, int64_t B, int64_t 
   a.perm = nullptr;
   if (ordered) {
     int32_t* perm = reinterpret_cast<int32_t*>(ws + ck_doubles + st_doubles);
-    e = zmpc_kick_order(kick, kick_steps, kick_step, B, perm,
+    e = zmpc_kick_order(c.kick, c.kick_steps, c.kick_step, B, perm,
                         ws + ck_doubles + st_doubles + perm_doubles, s);
     a.perm = perm;
   }
@@ -1479,10 +1462,10 @@ hipError_t zmpc_launch_rollout_strict_lq(const zmpc_plan* p, int64_t B, int64_t 
     if (runs) {
       a.rs = hl;
       a.rt = reinterpret_cast<int*>(hl + 2 * a.groups * a.rstride);
-      e = stage_runs(zmax, zmin, bstride, 2, 1, n, Bst, 2, hl, const_cast<int*>(a.rt), a.rstride,
-                     s, perm);
+      e = stage_runs(c.zmax, c.zmin, c.bstride, 2, 1, n, Bst, 2, hl, const_cast<int*>(a.rt),
+                     a.rstride, s, perm);
     } else {
-      e = stage(zmax, zmin, bstride, 2, 1, n, Bst, a.rows, 2, hl, s, perm);
+      e = stage(c.zmax, c.zmin, c.bstride, 2, 1, n, Bst, a.rows, 2, hl, s, perm);
       a.hl = hl;
     }
   }
@@ -1491,10 +1474,9 @@ hipError_t zmpc_launch_rollout_strict_lq(const zmpc_plan* p, int64_t B, int64_t 
   return e != hipSuccess ? e : ef;
 }
 
-hipError_t zmpc_launch_step_strict_lq(const zmpc_plan* p, int64_t B, const double* x,
-                                      const double* zmax_win, const double* zmin_win,
-                                      double* x_next, int32_t* status, hipStream_t s,
+hipError_t zmpc_launch_step_strict_lq(const zmpc_plan* p, const StepCall& c, hipStream_t s,
                                       std::string* why) {
+  const int64_t B = c.B;
   LqArgs a{};
   fill_consts(p, a);
   a.window_mode = 1;
@@ -1502,18 +1484,17 @@ hipError_t zmpc_launch_step_strict_lq(const zmpc_plan* p, int64_t B, const doubl
   a.n = p->N;
   a.nsteps = 1;
   a.B = B;
-  a.x0 = x;
+  a.x0 = c.x;
   a.kick = nullptr;
   a.kick_step = -1;
-  a.out = x_next;
-  a.status = status;
+  a.out = c.x_next;
+  a.status = c.status;
   a.shared = 0;
   a.groups = (B + 63) / 64;
   a.rows = (int64_t)a.NS * LQ_S;
   const int64_t waves = (B + 63) / 64;
-  const LqVariant* var = lq_variant_for(p->N);
-  if (!var) return hipErrorInvalidValue;
-  const int64_t G = var->G;  // checkpoints for every wave of the launched blocks
+  const int64_t G = lq_shape(p->N).G;  // checkpoints for every wave of the launched blocks
+  if (G == 0) return hipErrorInvalidValue;
   const size_t ck_doubles = (size_t)((waves + G - 1) / G * G) * a.NS * kCkStride;
   const size_t st_doubles = (size_t)a.groups * a.rows * 64 * 2;  // (hi, lo)
   double* ws = nullptr;
@@ -1524,7 +1505,7 @@ hipError_t zmpc_launch_step_strict_lq(const zmpc_plan* p, int64_t B, const doubl
   hipError_t e = hipSuccess;
   a.ck = ws;
   double2* hl = reinterpret_cast<double2*>(ws + ck_doubles);
-  e = stage(zmax_win, zmin_win, p->N, 1, 0, p->N, B, a.rows, 1, hl, s);
+  e = stage(c.zmax_win, c.zmin_win, p->N, 1, 0, p->N, B, a.rows, 1, hl, s);
   a.hl = hl;
   if (e == hipSuccess) e = launch_lq(p, a, waves, s);
   hipError_t ef = hipFreeAsync(ws, s);

@@ -44,10 +44,7 @@ namespace {
 using namespace zmpc_eta;
 
 constexpr int SC_MAXIT = 1024;  // active-set pass cap (as strict_lq.hip)
-// horizons of the kernel: 32-lane instances to N = 512 (C ≤ 16 slots per lane: 256 VGPRs + 248
-// AGPRs), whole-wave ones to 960 (C ≤ 15: 256 + 236; C = 16 of 64 lanes spills 12 B to scratch)
-constexpr int kScan32MaxN = 512;
-constexpr int kScanMaxN = 960;
+// (the horizons of the kernel, kScan32MaxN and kScanMaxN, are in dispatch.h)
 
 struct ScanArgs {
   int N;
@@ -693,28 +690,20 @@ void fill(const zmpc_plan* p, ScanArgs& a) {
   a.cnt = p->lqcnt;
 }
 
-// Lanes per instance: a whole wave while the instances fit one wave per SIMD (the latency of
-// one pass is what counts), 32 beyond (two instances per wave; chunks of up to 16 slots,
-// N ≤ 512; whole-wave instances beyond, to N = 960: N = 330–510 at 1024 walks 8.3e7–9.1e7 → 1.26e8–1.40e8 solves/s, profiles/r5aa/).  Chunks of C ≥ 3 slots per lane hold 1 wave per SIMD (their state spills past 256
-// VGPRs into AGPRs instead of scratch: __launch_bounds__ above), shorter ones 2.  (C = 3 at 2
-// waves per SIMD spilled 12 B to scratch; 1024 walks at N = 150, 32 lanes at one wave per
-// SIMD: 10.2 → 6.2 ms, profiles/r5q/.)
-int lanes_per_instance(const zmpc_plan* p, int64_t ninst) {
-  const int64_t cus = p->cus > 0 ? p->cus : 256;
-  // (one instance per SIMD: at N ≤ 128 the whole-wave instances would fit two waves per SIMD,
-  // but two instances per wave already run 1.6–1.8× faster there, profiles/r5t/)
-  return (ninst > cus * 4 && p->N <= kScan32MaxN) ? 32 : 64;
-}
-
-hipError_t launch(const zmpc_plan* p, const ScanArgs& a, hipStream_t s, int L) {
+// The kernel instance of dispatch.h scan_shape (lanes per instance, slots per lane).  Chunks of
+// C ≥ 3 slots per lane hold 1 wave per SIMD (their state spills past 256 VGPRs into AGPRs instead
+// of scratch: __launch_bounds__ above), shorter ones 2.  (C = 3 at 2 waves per SIMD spilled 12 B
+// to scratch; 1024 walks at N = 150, 32 lanes at one wave per SIMD: 10.2 → 6.2 ms, profiles/r5q/.)
+hipError_t launch(const zmpc_plan* p, const ScanArgs& a, hipStream_t s) {
+  const ScanShape shape = scan_shape(p->N, a.ninst, p->cus);
   const dim3 blk(64);
   int cmin = 1;
 #ifdef ZMPC_DIAG
   if (const char* e = getenv("ZMPC_SCAN_CMIN")) cmin = atoi(e);  // (diagnostics: wider chunks)
 #endif
-  if (L == 32) {
+  if (shape.lanes == 32) {
     const dim3 grid((unsigned)((a.ninst + 1) / 2));
-    switch (std::max((p->N + 31) / 32, std::min(cmin, 16))) {
+    switch (std::max(shape.C, std::min(cmin, 16))) {
 #define ZMPC_SCASE(CC)                                                        \
   case CC:                                                                    \
     hipLaunchKernelGGL((zmpc_strict_scan_kernel<CC, 32>), grid, blk, 0, s, a); \
@@ -729,7 +718,7 @@ hipError_t launch(const zmpc_plan* p, const ScanArgs& a, hipStream_t s, int L) {
     return hipGetLastError();
   }
   const dim3 grid((unsigned)a.ninst);
-  switch ((p->N + 63) / 64) {
+  switch (shape.C) {
 #define ZMPC_SCASE(CC)                                                        \
   case CC:                                                                    \
     hipLaunchKernelGGL((zmpc_strict_scan_kernel<CC, 64>), grid, blk, 0, s, a); \
@@ -746,64 +735,58 @@ hipError_t launch(const zmpc_plan* p, const ScanArgs& a, hipStream_t s, int L) {
 
 }  // namespace
 
-bool zmpc_strict_scan_supported(const zmpc_plan* p) { return p->N >= 1 && p->N <= kScanMaxN; }
+bool zmpc_strict_scan_supported(const zmpc_plan* p) { return strict_scan_supported(p->N); }
 
-hipError_t zmpc_launch_rollout_strict_scan(const zmpc_plan* p, int64_t B, int64_t n,
-                                           const double* zmax, const double* zmin,
-                                           int64_t bstride, const double* x0, const double* kick,
-                                           int64_t kick_step, const int64_t* kick_steps,
-                                           double* hist, int32_t* status, hipStream_t s,
-                                           std::string* why) {
+hipError_t zmpc_launch_rollout_strict_scan(const zmpc_plan* p, const RolloutCall& c,
+                                           hipStream_t s, std::string* why) {
   if (!zmpc_strict_scan_supported(p)) {
-    *why = "the small-batch strict kernel supports horizons N <= 960";
+    *why = "the small-batch strict kernel supports horizons N <= " + std::to_string(kScanMaxN);
     return hipErrorInvalidValue;
   }
-  if (status) {
-    hipError_t e = hipMemsetAsync(status, 0, sizeof(int32_t) * B, s);
+  if (c.status) {
+    hipError_t e = hipMemsetAsync(c.status, 0, sizeof(int32_t) * c.B, s);
     if (e != hipSuccess) return e;
   }
-  if (B == 0) return hipSuccess;
+  if (c.B == 0) return hipSuccess;
   ScanArgs a{};
   fill(p, a);
   a.window_mode = 0;
   a.toff = 1;
-  a.n = n;
-  a.nsteps = n - 1;
-  a.ninst = 2 * B;
-  a.zmax = zmax;
-  a.zmin = zmin;
-  a.bstride = bstride;
-  a.x0 = x0;
-  a.kick = kick;
-  a.kick_step = kick_step;
-  a.kick_steps = kick_steps;
-  a.out = hist;
-  a.status = status;
-  return launch(p, a, s, lanes_per_instance(p, a.ninst));
+  a.n = c.n;
+  a.nsteps = c.n - 1;
+  a.ninst = 2 * c.B;
+  a.zmax = c.zmax;
+  a.zmin = c.zmin;
+  a.bstride = c.bstride;
+  a.x0 = c.x0;
+  a.kick = c.kick;
+  a.kick_step = c.kick_step;
+  a.kick_steps = c.kick_steps;
+  a.out = c.hist;
+  a.status = c.status;
+  return launch(p, a, s);
 }
 
-hipError_t zmpc_launch_step_strict_scan(const zmpc_plan* p, int64_t B, const double* x,
-                                        const double* zmax_win, const double* zmin_win,
-                                        double* x_next, int32_t* status, hipStream_t s,
+hipError_t zmpc_launch_step_strict_scan(const zmpc_plan* p, const StepCall& c, hipStream_t s,
                                         std::string* why) {
   if (!zmpc_strict_scan_supported(p)) {
-    *why = "the small-batch strict kernel supports horizons N <= 960";
+    *why = "the small-batch strict kernel supports horizons N <= " + std::to_string(kScanMaxN);
     return hipErrorInvalidValue;
   }
-  if (B == 0) return hipSuccess;
+  if (c.B == 0) return hipSuccess;
   ScanArgs a{};
   fill(p, a);
   a.window_mode = 1;
   a.toff = 0;
   a.n = 0;
   a.nsteps = 1;
-  a.ninst = B;
-  a.zmax = zmax_win;
-  a.zmin = zmin_win;
+  a.ninst = c.B;
+  a.zmax = c.zmax_win;
+  a.zmin = c.zmin_win;
   a.bstride = 0;
-  a.x0 = x;
-  a.out = x_next;
-  a.status = status;
+  a.x0 = c.x;
+  a.out = c.x_next;
+  a.status = c.status;
   a.kick_step = -1;
-  return launch(p, a, s, lanes_per_instance(p, a.ninst));
+  return launch(p, a, s);
 }

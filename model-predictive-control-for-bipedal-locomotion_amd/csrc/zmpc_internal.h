@@ -6,6 +6,7 @@
 
 #include <string>
 
+#include "dispatch.h"
 #include "zmpc.h"
 
 // Scalar LIPM constants of zmp_controller.py:18-20 (A = [[1,T,T²/2],[0,1,T],[0,0,1]],
@@ -21,11 +22,6 @@ constexpr int kScanPowOff = 8 * kScanStride;
 // lane's chunk end state Σ_q Ā^(C−1−q) B f_q, and the kick's Ā^(C−1−q) e1)
 constexpr int kScanGOff = kScanPowOff + 8 * 33 * 9;
 constexpr int kScanDoubles = kScanGOff + 8 * 6;
-
-// Longest strict horizon of the LQ kernel (strict_lq.hip lq_variant_for: its per-wave LDS —
-// slot flags, 2 bits per slot and lane since round 6, and the parked V and state — fits a CU at
-// two waves per workgroup, checked there by a static_assert); unchanged since round 5.
-constexpr int ZMPC_STRICT_MAX_N = 2464;
 
 struct LipmConsts {
   double T;     // A[0,1] = A[1,2] = B[2]
@@ -79,15 +75,29 @@ struct zmpc_plan {
 // rows of the fast-FIR tap table: m = 0..⌈(N+1)/2⌉−1, plus zero rows for an unrolled loop
 __host__ __device__ constexpr int kffa_rows(int N) { return (N + 2) / 2 + 8; }
 
-// suffix sums S_j = Σ_{j' ≥ j} k_{j'} of the gain row: entry i = S_{i−8} for 1 ≤ i − 8 ≤ N − 1,
-// zero elsewhere in [0, N + 16) (so a lane's 8-wide read at any clamped offset stays inside),
-// S_0 at N + 16
-__host__ __device__ constexpr int ksum_rows(int N) { return N + 18; }
-__host__ __device__ constexpr int ksum_s0(int N) { return N + 16; }
+// (ksum_rows / ksum_s0, the layout of the suffix sums of k, and the FFT table sizes kFftPT,
+// kFftPmin, kFftGComplex are in dispatch.h: they enter the LDS budgets of the launch rules)
 
-constexpr int kFftPT = 8192;    // largest transform (twiddle table size)
-constexpr int kFftPmin = 256;   // smallest transform with a gain spectrum
-constexpr int kFftGComplex = 2 * kFftPT - kFftPmin;  // Σ_P P over P = kFftPmin..kFftPT
+// The arguments of one zmpc_rollout / zmpc_rollout_kicks call (include/zmpc.h), filled once in
+// capi.hip and handed down by reference.
+struct RolloutCall {
+  int64_t B, n;
+  const double *zmax, *zmin;
+  int64_t bstride;  // bounds stride in doubles, 0: one shared CoP
+  const double *x0, *kick;
+  int64_t kick_step;
+  const int64_t* kick_steps;  // per-walk kick steps, or null: kick_step
+  double* hist;
+  int32_t* status;  // may be null
+};
+
+// The arguments of one zmpc_step call.
+struct StepCall {
+  int64_t B;
+  const double *x, *zmax_win, *zmin_win;
+  double* x_next;
+  int32_t* status;  // may be null
+};
 
 // kernels launchers (plan.hip); ev (may be NULL): ZMPC_PLAN_STAGES events, ev[0] recorded
 // before the first stage and ev[i + 1] after stage i for stages 0..9 of include/zmpc.h
@@ -107,37 +117,32 @@ hipError_t zmpc_launch_walk_metrics(const zmpc_plan* p, int64_t B, int64_t n, co
                                     const int64_t* lengths, double* metrics, hipStream_t s);
 
 // unconstrained rollout / step (rollout.hip)
-hipError_t zmpc_launch_rollout_unc(const zmpc_plan* p, int64_t B, int64_t n, const double* zmax,
-                                   const double* zmin, int64_t bstride, const double* x0,
-                                   const double* kick, int64_t kick_step,
-                                   const int64_t* kick_steps, double* hist, int32_t* status,
-                                   hipStream_t s, std::string* why);
-hipError_t zmpc_launch_step_unc(const zmpc_plan* p, int64_t B, const double* x,
-                                const double* zmax_win, const double* zmin_win, double* x_next,
-                                int32_t* status, hipStream_t s);
+hipError_t zmpc_launch_rollout_unc(const zmpc_plan* p, const RolloutCall& c, hipStream_t s,
+                                   std::string* why);
+hipError_t zmpc_launch_step_unc(const zmpc_plan* p, const StepCall& c, hipStream_t s);
 
-// strict box-QP rollout / step (strict.hip)
-hipError_t zmpc_launch_rollout_strict(const zmpc_plan* p, int64_t B, int64_t n,
-                                      const double* zmax, const double* zmin, int64_t bstride,
-                                      const double* x0,
-                                      const double* kick, int64_t kick_step,
-                                      const int64_t* kick_steps, double* hist,
-                                      int32_t* status, hipStream_t s, std::string* why);
-hipError_t zmpc_launch_step_strict(const zmpc_plan* p, int64_t B, const double* x,
-                                   const double* zmax_win, const double* zmin_win,
-                                   double* x_next, int32_t* status, hipStream_t s,
+// strict box-QP rollout / step: the solver of the launch by dispatch.h choose_strict, then its
+// backend below (strict_dispatch.hip)
+hipError_t zmpc_launch_rollout_strict(const zmpc_plan* p, const RolloutCall& c, hipStream_t s,
+                                      std::string* why);
+hipError_t zmpc_launch_step_strict(const zmpc_plan* p, const StepCall& c, hipStream_t s,
                                    std::string* why);
 
+// strict box-QP by reduced Cholesky (strict.hip): the tile kernel (16 instances per workgroup) and
+// the one-instance-per-wave kernel, N <= kStrictCholMaxN; cross-checks of the two below
+hipError_t zmpc_launch_rollout_strict_tile(const zmpc_plan* p, const RolloutCall& c,
+                                           hipStream_t s, std::string* why);
+hipError_t zmpc_launch_step_strict_tile(const zmpc_plan* p, const StepCall& c, hipStream_t s,
+                                        std::string* why);
+hipError_t zmpc_launch_rollout_strict_wave(const zmpc_plan* p, const RolloutCall& c,
+                                           hipStream_t s, std::string* why);
+hipError_t zmpc_launch_step_strict_wave(const zmpc_plan* p, const StepCall& c, hipStream_t s,
+                                        std::string* why);
+
 // strict box-QP in LQ form, one instance per lane (strict_lq.hip); the default strict path
-hipError_t zmpc_launch_rollout_strict_lq(const zmpc_plan* p, int64_t B, int64_t n,
-                                         const double* zmax, const double* zmin,
-                                         int64_t bstride, const double* x0, const double* kick,
-                                         int64_t kick_step, const int64_t* kick_steps,
-                                         double* hist, int32_t* status, hipStream_t s,
+hipError_t zmpc_launch_rollout_strict_lq(const zmpc_plan* p, const RolloutCall& c, hipStream_t s,
                                          std::string* why);
-hipError_t zmpc_launch_step_strict_lq(const zmpc_plan* p, int64_t B, const double* x,
-                                      const double* zmax_win, const double* zmin_win,
-                                      double* x_next, int32_t* status, hipStream_t s,
+hipError_t zmpc_launch_step_strict_lq(const zmpc_plan* p, const StepCall& c, hipStream_t s,
                                       std::string* why);
 bool zmpc_strict_lq_supported(const zmpc_plan* p);
 hipError_t zmpc_strict_lq_set_attrs();
@@ -145,15 +150,9 @@ size_t zmpc_strict_lq_table_doubles(int N);
 hipError_t zmpc_strict_lq_build_table(zmpc_plan* p, hipStream_t s);
 
 // strict box-QP for small batches, one instance per wave, parallel in time (strict_scan.hip)
-hipError_t zmpc_launch_rollout_strict_scan(const zmpc_plan* p, int64_t B, int64_t n,
-                                           const double* zmax, const double* zmin,
-                                           int64_t bstride, const double* x0, const double* kick,
-                                           int64_t kick_step, const int64_t* kick_steps,
-                                           double* hist, int32_t* status, hipStream_t s,
-                                           std::string* why);
-hipError_t zmpc_launch_step_strict_scan(const zmpc_plan* p, int64_t B, const double* x,
-                                        const double* zmax_win, const double* zmin_win,
-                                        double* x_next, int32_t* status, hipStream_t s,
+hipError_t zmpc_launch_rollout_strict_scan(const zmpc_plan* p, const RolloutCall& c,
+                                           hipStream_t s, std::string* why);
+hipError_t zmpc_launch_step_strict_scan(const zmpc_plan* p, const StepCall& c, hipStream_t s,
                                         std::string* why);
 bool zmpc_strict_scan_supported(const zmpc_plan* p);
 
@@ -177,6 +176,3 @@ hipError_t zmpc_herdt_set_attrs();
 
 hipError_t zmpc_rollout_unc_set_attrs();
 hipError_t zmpc_strict_set_attrs();
-
-// Dynamic LDS the rollout kernel needs for (N, n); 0 if it does not fit a CU.
-size_t zmpc_rollout_unc_lds_bytes(int Kpad, int64_t n);

@@ -426,11 +426,13 @@ def test_multi_walk_workgroups_vs_oracle(n):
 
 
 def test_rollout_kernel_variants_agree():
-    """The default single-pass kernels (split per axis: one walk per workgroup, the fast-FIR or
-    sparse correlation; persistent for even chunk widths) and the cross-check kernel (one wave
-    per walk, direct correlation: ZMPC_OPT_ROLLOUT_KERNEL = 1) agree, at an odd (n = 420: 7)
-    and an even (n = 360: 6) chunk width, and at n = 480 (chunk width 8: per-walk bounds take
-    the wide kernel), with per-walk and shared CoP."""
+    """The default single-pass kernels (csrc/dispatch.h choose_unc: Split for per-walk bounds, a
+    workgroup of one wave per axis per walk with the sparse correlation first and the fast-FIR
+    dense form at odd chunk widths; SplitShared for a shared CoP, f computed once per launch) and
+    the cross-check kernel (Generic: one wave per walk, direct correlation,
+    ZMPC_OPT_ROLLOUT_KERNEL = 1) agree, at an odd (n = 420: 7) and an even (n = 360: 6) chunk
+    width, and at n = 480 (chunk width 8, still the single-pass split kernel: the wide kernel
+    starts at n = 514), with per-walk and shared CoP."""
     for Nn, n_cut in ((150, None), (150, 360), (512, 480)):
         zmax, zmin, x0, F, dt = synthetic_batch(4133 if Nn == 150 else 1031, Nn)
         if n_cut:
@@ -939,9 +941,10 @@ def test_strict_long_horizon_rollout_vs_oracle():
 @pytest.mark.parametrize("N,solver", ((400, 3), (400, 4), (700, 3), (700, 4), (1300, 0)))
 def test_strict_long_horizon_step_vs_oracle(N, solver):
     """Cold-start strict solves, vs the reference's own strict calls (strict_long_ref.npz): the
-    LQ kernel (3) at horizons it runs with 4, 2 and 1 waves per workgroup, the parallel-in-time
-    kernel (4) with whole-wave instances to N = 960 (C = 7 and 11 slots per lane), and the
-    automatic choice beyond it (N = 1300: the LQ kernel)."""
+    LQ kernel (3) in its 8-wave workgroups with one LDS checkpoint per wave (N = 400) and none
+    (N = 700) (csrc/dispatch.h lq_shape), the parallel-in-time kernel (4) with whole-wave
+    instances (C = 7 and 11 slots per lane, scan_shape), and the automatic choice beyond that
+    kernel's N = 960 (N = 1300: the LQ kernel, 4-wave workgroups with two LDS checkpoints)."""
     d = golden("strict_long_ref.npz")
     p = plan(N, strict=True)
     if solver:
@@ -1042,9 +1045,10 @@ def test_strict_weights_long_horizon(w, solver):
     (tests/golden/strict_weights_long_ref.npz, make_strict_ref_golden.py --weights-long): the
     reference's strict branch on 200 samples of the default walk's stepping phase at N = 400 with
     an 800 N kick, and 8 cold heavily-active calls at N = 700.  Both kernels (3: the LQ kernel
-    with 4-wave workgroups at N = 400, 2 at 700; 4: whole-wave scan instances, 7 and 11 slots
-    per lane): CoM RMSE ≤ 1e-9 and single solves ≤ 1e-7 relative, as the default-weight long
-    fixtures (test_strict_long_horizon_*), every status 0."""
+    with 8-wave workgroups, one LDS checkpoint per wave at N = 400 and none at 700, csrc/dispatch.h
+    lq_shape; 4: whole-wave scan instances, 7 and 11 slots per lane): CoM RMSE ≤ 1e-9 and single
+    solves ≤ 1e-7 relative, as the default-weight long fixtures (test_strict_long_horizon_*),
+    every status 0."""
     d = golden("strict_weights_long_ref.npz")
     Qv, Rv, hv, gv = (float(v) for v in d["weights"][w])
     N = 400
