@@ -674,7 +674,7 @@ __device__ __forceinline__ bool axis_correlate_sparse(const RolloutArgs& a, cons
 // raised wave priority, so a CU's co-resident walks get their memory traffic out ahead of the
 // others' correlation (config 2: 45.3 → 43.8 µs; the one-walk-per-workgroup grid is not helped).
 // FFA: odd chunk widths take the two-parallel fast-FIR form of the dense correlation.
-template <int CW, bool SHF, bool PM, bool FFA>
+template <int CW, bool SHF, bool PM, bool FFA, bool PFB>
 __device__ __forceinline__ void split_walk(const RolloutArgs& a, int64_t b, double* smem,
                                            int* flag, const double* __restrict__ kg,
                                            const double* __restrict__ scanP,
@@ -683,56 +683,79 @@ __device__ __forceinline__ void split_walk(const RolloutArgs& a, int64_t b, doub
   using ZL = ZrLayout<CW>;
   const int tid = threadIdx.x, lane = tid & 63, axis = tid >> 6;
   const int n = a.n, nsteps = n - 1;
+  const double* Gc = scanP + kScanGOff;  // the chunk-sum columns Ā^p B, Ā^p e1
   double f[CW];
   double pf0 = 0.0, pf1 = 0.0;  // prefetch results (kept alive to the end, never used)
+  AxisBounds<CW> r;
+  double2 hl, ll;
+  double ts0 = 0.0, ts1 = 0.0;  // this thread's two rows of the suffix-sum table
   tl_stamp(a, b, 0);
+  // ---- 1. loads ------------------------------------------------------------------------------
+  // Every global load of the walk is issued here, before the first wait, as straight-line code
+  // (clamped indices, no runtime branch around a load): the compiler then waits with exact
+  // partial counts, and the walk's own data is one memory round trip away.  Order: x0 and kick,
+  // the bounds, the last sample (wave-uniform: scalar loads), the table rows.
+  if constexpr (PM && !SHF) __builtin_amdgcn_s_setprio(3);  // issue the walk's loads first
   const double* xb = a.x0 + b * 6 + 3 * axis;
   const double xi[3] = {xb[0], xb[1], xb[2]};
-  const double kk = (axis == 1 && a.kick != nullptr) ? a.kick[b] : 0.0;
+  const double kks = (a.kick != nullptr) ? a.kick[b] : 0.0;  // wave-uniform: a scalar load
   if constexpr (SHF) {
     // shared CoP: f of this lane's timesteps, computed once per launch (zmpc_shared_f_kernel)
     const double* fp = a.fsh + axis * a.fstride + lane * CW;
 #pragma unroll
     for (int q = 0; q < CW; ++q) f[q] = fp[q];
   } else {
+    axis_load<CW>(a, b, tid, r);
+    hl = reinterpret_cast<const double2*>(a.zmax + b * a.bstride)[n - 1];
+    ll = reinterpret_cast<const double2*>(a.zmin + b * a.bstride)[n - 1];
+    // rows tid and tid + 128 of the plan's suffix-sum table (sparse-difference correlation), into
+    // LDS with the z_ref rows below; without the table (dense plans) the loads read row 0 of k
+    {
+      const double* tp = a.ksum != nullptr ? a.ksum : kg;
+      const int tl = a.ksum != nullptr ? ksum_rows(a.hN) - 1 : 0;
+      ts0 = tp[min(tid, tl)];
+      ts1 = tp[min(tid + 128, tl)];
+    }
+  }
+  if constexpr (PM && !SHF) __builtin_amdgcn_s_setprio(0);
+  // The kick, all wave-uniform and on the scalar unit: the lane kl that owns the kick step, the
+  // step's place qk in that lane's chunk and the kick's chunk-sum column Ā^(CW−1−qk) e1.  Only the
+  // y wave of a walk whose kick step is one of its nsteps steps is `kicked`.
+  const bool ywave = __builtin_amdgcn_readfirstlane(axis) != 0;
+  const int64_t kick_step = kick_step_of(a, b);
+  const bool kicked = ywave && kick_step >= 0 && kick_step < nsteps;
+  const int ksi = kicked ? (int)kick_step : 0;
+  const int kl = ksi / CW, qk0 = ksi - kl * CW, qk = kicked ? qk0 : -1;
+  const double* ekp = Gc + (CW - 1 - qk0) * 6 + 3;
+  const double ek[3] = {ekp[0], ekp[1], ekp[2]};
+  const double kk = (kicked && lane == kl) ? kks : 0.0;  // the kick on its lane, +0.0 elsewhere
+  if constexpr (!SHF) {
     double* zr0 = smem;
     double* zr1 = zr0 + a.lzp;
-    // ---- 1. loads --------------------------------------------------------------------------
-    if constexpr (PM) __builtin_amdgcn_s_setprio(3);  // issue the walk's loads first
-    AxisBounds<CW> r;
-    axis_load<CW>(a, b, tid, r);
-    const double2 hl = reinterpret_cast<const double2*>(a.zmax + b * a.bstride)[n - 1];
-    const double2 ll = reinterpret_cast<const double2*>(a.zmin + b * a.bstride)[n - 1];
-    // the plan's suffix-sum table (sparse-difference correlation) behind the two z_ref areas
-    double* Ts = smem + 2 * a.lzp;
-    if (a.ksum != nullptr)
-      for (int i = tid; i < ksum_rows(a.hN); i += 128) Ts[i] = a.ksum[i];
-    // the bounds of the walk the next dispatch round puts on this slot, one double per 64 B
-    // (threads 0..63 z_max, 64..127 z_min; two loads cover n ≤ 512 samples), so that round's
-    // loads hit L2 / Infinity Cache instead of HBM under this round's compute (issued after the
-    // walk's own loads have landed it gained nothing: 29.9 vs 29.5 µs, profiles/r3pf2/)
-    if (a.pf_ahead > 0 && b + a.pf_ahead < a.B) {
-      const double* src = (tid < 64 ? a.zmax : a.zmin) + (b + a.pf_ahead) * a.bstride;
-      const int ln = tid & 63, nd = 2 * n;
-      pf0 = src[min(ln * 8, nd - 1)];
-      pf1 = src[min(ln * 8 + 512, nd - 1)];
-    }
-    if constexpr (PM) __builtin_amdgcn_s_setprio(0);
-    // ---- 2. z_ref rows + window padding (zmp_controller.py:81-88) --------------------------
+    double* Ts = smem + 2 * a.lzp;  // the suffix-sum table behind the two z_ref areas
+    // ---- 2. z_ref rows + window padding (zmp_controller.py:81-88), table rows ----------------
+    // Branch-free, so that the bound loads stay up front (under `if (t < n)` the compiler sinks
+    // a round's loads into the branch, behind a full drain): a thread past the walk's end holds
+    // the clamped load of the last sample, which is the padding value of its own row t < lz.
+    constexpr int kRows = 128 * AxisBounds<CW>::PF2;  // ≥ n: the rows these stores cover
 #pragma unroll
     for (int u = 0; u < AxisBounds<CW>::PF2; ++u) {
-      const int t = u * 128 + tid;
-      if (t < n) {
-        zr0[ZL::idx(t)] = (r.hi[u].x + r.lo[u].x) / 2;
-        zr1[ZL::idx(t)] = (r.hi[u].y + r.lo[u].y) / 2;
-      }
+      const int t = min(u * 128 + tid, a.lz - 1);
+      zr0[ZL::idx(t)] = (r.hi[u].x + r.lo[u].x) / 2;
+      zr1[ZL::idx(t)] = (r.hi[u].y + r.lo[u].y) / 2;
     }
     {
       const double l0 = (hl.x + ll.x) / 2, l1 = (hl.y + ll.y) / 2;
-      for (int t = n + tid; t < a.lz; t += 128) {
+      for (int t = kRows + tid; t < a.lz; t += 128) {
         zr0[ZL::idx(t)] = l0;
         zr1[ZL::idx(t)] = l1;
       }
+    }
+    if (a.ksum != nullptr) {
+      const int rows = ksum_rows(a.hN);
+      if (tid < rows) Ts[tid] = ts0;
+      if (tid + 128 < rows) Ts[tid + 128] = ts1;
+      for (int i = tid + 256; i < rows; i += 128) Ts[i] = a.ksum[i];  // N > 238 only
     }
     __syncthreads();
     tl_stamp(a, b, 1);
@@ -747,9 +770,28 @@ __device__ __forceinline__ void split_walk(const RolloutArgs& a, int64_t b, doub
       axis_correlate<CW>(a, kg, axis ? zr1 : zr0, lane, f);  // k: wave-uniform scalar loads
     __syncthreads();  // z_ref dead: the area becomes the history staging (n rows of 6)
     tl_stamp(a, b, 2);
+    // ---- the next dispatch round's bounds -----------------------------------------------------
+    // The bounds of the walk the next dispatch round puts on this slot, one double per 64 B
+    // (threads 0..63 z_max, 64..127 z_min; two loads cover n ≤ 512 samples), so that round's
+    // loads hit L2 / Infinity Cache instead of HBM.  PFB is the launcher's pf_ahead > 0; the walk
+    // index is clamped (the last round's workgroups touch walk B − 1 again), so the loads are
+    // straight-line code and no wait before either barrier covers them (the scan's first wait, for
+    // its per-lane powers, does: they follow in the in-order counter).  They are issued here,
+    // after the correlation: the first round's load phase is bound by HBM bandwidth (all resident
+    // workgroups load at once), so prefetch traffic beside the walks' own loads only delays them,
+    // while the scan and replay that follow use no global memory (config 2, same box: beside the
+    // own loads 27.1–27.3 µs, after the first barrier 25.7–26.2, here 25.0–25.7, before the replay
+    // 26.1–26.7, after the third barrier 26.0–26.4; profiles/r7/loadphase/).  Up to round 6 they
+    // sat before the first barrier behind a runtime branch and the table loop's drain, so every
+    // first-round wave waited for them before its correlation (27.0–27.3 µs).
+    if constexpr (PFB) {
+      const double* src = (tid < 64 ? a.zmax : a.zmin) + min(b + a.pf_ahead, a.B - 1) * a.bstride;
+      const int ln = tid & 63, nd = 2 * n;
+      pf0 = src[min(ln * 8, nd - 1)];
+      pf1 = src[min(ln * 8 + 512, nd - 1)];
+    }
   }
   // ---- 4. lane-chunk affine scan -----------------------------------------------------------
-  const int64_t kick_step = (axis == 1) ? kick_step_of(a, b) : -1;
   const LipmConsts lc = a.lc;
   const double kx0 = kxp[0], kx1 = kxp[1], kx2 = kxp[2];
   const int mbeg = lane * CW;
@@ -758,18 +800,17 @@ __device__ __forceinline__ void split_walk(const RolloutArgs& a, int64_t b, doub
     // the chunk's end state from a zero start as one sum, Σ_q Ā^(CW−1−q) B f_q (plan columns;
     // 3 FMAs per step instead of the 12 of the recursion), plus the kick's −kk Ā^(CW−1−q) e1.
     // Steps past nsteps count too: only lanes whose chunk holds no output follow such a lane.
-    const double* Gc = scanP + kScanGOff;
 #pragma unroll
     for (int q = 0; q < CW; ++q) {
       const double* gq = Gc + (CW - 1 - q) * 6;
 #pragma unroll
       for (int i = 0; i < 3; ++i) sv[i] = fma(gq[i], f[q], sv[i]);
     }
-    const int64_t qk = kick_step - mbeg;
-    if (qk >= 0 && qk < CW && kick_step < nsteps) {
-      const double* ek = Gc + (CW - 1 - (int)qk) * 6 + 3;
+    if (kicked) {
+      if (lane == kl) {
 #pragma unroll
-      for (int i = 0; i < 3; ++i) sv[i] = fma(-kk, ek[i], sv[i]);
+        for (int i = 0; i < 3; ++i) sv[i] = fma(-kk, ek[i], sv[i]);
+      }
     }
   }
   const double* Pp = scanP + (CW - 1) * kScanStride;  // (Ā^CW)^(2^r), r = 0..5, from the plan
@@ -795,6 +836,10 @@ __device__ __forceinline__ void split_walk(const RolloutArgs& a, int64_t b, doub
     stage[3 * axis + 1] = xi[1];
     stage[3 * axis + 2] = xi[2];
   }
+  // The kick is a wave-uniform test on the step's place in the chunk (qk = −1 on a wave without a
+  // kick: a scalar compare per step): kk is the kick on lane kl and +0.0 on every other lane,
+  // which changes no value.  (A second copy of the replay without the test, taken by waves
+  // without a kick, cost the shared-CoP kernel 2 %: config 4 unconstrained 495 vs 486 µs.)
 #pragma unroll
   for (int q = 0; q < CW; ++q) {
     const int m = mbeg + q;
@@ -802,7 +847,7 @@ __device__ __forceinline__ void split_walk(const RolloutArgs& a, int64_t b, doub
       const double u = f[q] - (kx0 * x[0] + kx1 * x[1] + kx2 * x[2]);
       double xn[3];
       lipm_step(lc, x, u, xn);
-      if (m == kick_step) xn[1] -= kk;  // force kick (zmp_controller.py:90,105-106)
+      if (q == qk) xn[1] -= kk;  // force kick (zmp_controller.py:90,105-106)
       double* o = stage + HistLayout<CW>::row(m + 1) + 3 * axis;
       o[0] = xn[0];
       o[1] = xn[1];
@@ -891,19 +936,19 @@ __global__ void __launch_bounds__(128, 4)
   extern __shared__ __attribute__((aligned(16))) double smem[];
   __shared__ int flag[2];
   for (int64_t b = blockIdx.x; b < a.B; b += gridDim.x) {
-    split_walk<CW, false, true, false>(a, b, smem, flag, a.k, a.scanP, a.kx, a.hist);
+    split_walk<CW, false, true, false, false>(a, b, smem, flag, a.k, a.scanP, a.kx, a.hist);
     __syncthreads();  // staging read out before the next walk's z_ref overwrites it
   }
 }
 
 // One walk per workgroup (the default; odd chunk widths with the fast-FIR dense form), and the
-// shared-CoP form (SHF).
-template <int CW, bool SHF>
+// shared-CoP form (SHF).  PFB: with the next-dispatch-round prefetch (launch_unc: pf_ahead > 0).
+template <int CW, bool SHF, bool PFB = false>
 __global__ void __launch_bounds__(128, 4) zmpc_rollout_unc_splitd_kernel(RolloutArgs a) {
   extern __shared__ __attribute__((aligned(16))) double smem[];
   __shared__ int flag[2];
-  split_walk<CW, SHF, false, true>(a, blockIdx.x, smem, flag, (CW & 1) ? a.kffa : a.k, a.scanP,
-                                   a.kx, a.hist);
+  split_walk<CW, SHF, false, true, PFB>(a, blockIdx.x, smem, flag, (CW & 1) ? a.kffa : a.k,
+                                        a.scanP, a.kx, a.hist);
 }
 
 // ---- FFT correlation (long walks) ------------------------------------------------------------
@@ -1722,11 +1767,15 @@ void launch_unc(const UncChoice& c, hipStream_t s, RolloutArgs a, int cus) {
   }
 #endif
   const int occ = occupancy(
-      reinterpret_cast<const void*>(zmpc_rollout_unc_splitd_kernel<CW, false>), 128, c.lds);
+      reinterpret_cast<const void*>(zmpc_rollout_unc_splitd_kernel<CW, false, true>), 128, c.lds);
   const int64_t R = (int64_t)std::max(cus, 1) * occ;
   a.pf_ahead = (R > 0 && a.n <= 512 && a.B <= 2 * R) ? R : 0;
-  hipLaunchKernelGGL((zmpc_rollout_unc_splitd_kernel<CW, false>), dim3((unsigned)a.B),
-                     dim3(128), c.lds, s, a);
+  if (a.pf_ahead > 0)
+    hipLaunchKernelGGL((zmpc_rollout_unc_splitd_kernel<CW, false, true>), dim3((unsigned)a.B),
+                       dim3(128), c.lds, s, a);
+  else
+    hipLaunchKernelGGL((zmpc_rollout_unc_splitd_kernel<CW, false>), dim3((unsigned)a.B),
+                       dim3(128), c.lds, s, a);
 }
 
 }  // namespace
