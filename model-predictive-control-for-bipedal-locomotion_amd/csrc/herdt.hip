@@ -574,6 +574,17 @@ __global__ void __launch_bounds__(64) zmpc_herdt_kernel(HerdtArgs a) {
     int it = 0, own = 0;  // own: the passes this lane pair needed (diagnostics, ZMPC_HERDT_PROF)
     bool pair_done = false;
     bool again = true;  // (itmax: the most passes of one solve, counter [9])
+    // Anti-cycling safeguard of the block exchange (Júdice & Pires' block principal pivoting
+    // with Murty's least-index fallback): every pass exchanges all wrong rows at once while
+    // the count of wrong rows keeps reaching new lows, or for at most PFULL passes in a row
+    // that do not; after that a pass exchanges only the lane's first wrong row (least index)
+    // until a new low is reached.  The least-index rule ends on a fixed positive definite
+    // bound-constrained problem; here the two axes of a pair are coupled through the polytope
+    // solve, so this is a safeguard (it ended the one cycle met), not a proof: max_passes stays
+    // the last resort.  A pass without a wrong row starts the count over.
+    constexpr int PFULL = 8;
+    int ninf_best = 0x7fffffff, pfull = PFULL;
+    bool single = false;
     while (again) {
       const unsigned long long tp0 = (kProf && a.prof) ? clock64() : 0;
       // ---- sweep 1: backward Riccati over ξ = [x; f] for V_0(x, f), then the footsteps -----
@@ -743,6 +754,7 @@ __global__ void __launch_bounds__(64) zmpc_herdt_kernel(HerdtArgs a) {
       // Slab rows are loaded RB at a time: at one wave per SIMD nothing else hides the
       // latency of a row's loads.
       bool changed = false;
+      int ninf = 0;  // rows of this lane whose working-set flag is wrong after this pass
       const unsigned long long tp2 = (kProf && a.prof) ? clock64() : 0;
       {
         double xs[3] = {x[0], x[1], x[2]};
@@ -817,7 +829,8 @@ __global__ void __launch_bounds__(64) zmpc_herdt_kernel(HerdtArgs a) {
                 const bool drop = (wk == 1 && nu < -tn) || (wk == 2 && nu > tn);
                 const int nw = pin ? (drop ? 0 : wk) : (kd != CK_NONE ? nf : 0);
                 if (nw != wk) {
-                  wset[k * 64 + lane] = (unsigned char)nw;
+                  if (!single || ninf == 0) wset[k * 64 + lane] = (unsigned char)nw;
+                  ++ninf;
                   changed = true;
                 }
               }
@@ -841,6 +854,22 @@ __global__ void __launch_bounds__(64) zmpc_herdt_kernel(HerdtArgs a) {
         pr_f += tp2 - tp1;
         pr_fs += tpf - tp1;
         pr_w += tp3 - tp2;
+      }
+      if (ninf == 0) {
+        // converged for now, waiting for the wave or the partner axis: start over, so that rows
+        // the partner's footstep makes wrong again are exchanged as a block once more
+        ninf_best = 0x7fffffff;
+        pfull = PFULL;
+        single = false;
+      } else if (ninf < ninf_best) {
+        ninf_best = ninf;
+        pfull = PFULL;
+        single = false;
+      } else if (pfull > 0) {
+        --pfull;
+        single = false;
+      } else {
+        single = true;
       }
       ++it;
       ++n_wave_pass;

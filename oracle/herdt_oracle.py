@@ -318,8 +318,10 @@ def herdt_qp(cfg, x_init, y_init, v_ref, x_fc, y_fc, current, window, foot_side)
     return Q, p, G, np.array(rhs), N, m
 
 
-def herdt_solve(Q, p, G, h, N, m):
-    """Exact solution of herdt_qp's problem.  A footstep variable whose support segment lies
+def herdt_solve(Q, p, G, h, N, m, foot=None):
+    """Exact solution of herdt_qp's problem; foot = the current foot (x_fc, y_fc), which only
+    the rule below reads: it may be left out unless the first footstep's column is empty
+    (ValueError then).  A footstep variable whose support segment lies
     past the horizon (the reference's U column is empty: U[N:N+1]) does not enter the
     objective: it is fixed to the previous footstep, the first one to the point of the
     polytope nearest the current foot (OSQP's choice there is whatever its iterate was —
@@ -334,11 +336,14 @@ def herdt_solve(Q, p, G, h, N, m):
     for i in empty:
         keep[N + i] = keep[n1 + N + i] = False
     if 0 in empty:
+        if foot is None:
+            raise ValueError("herdt_solve: the first footstep's column is empty, so the "
+                             "current foot is needed to place it")
         # nearest polytope point to the current foot: rows of G on (f_x0, f_y0) only
         poly = np.where((np.abs(G[:, N]) + np.abs(G[:, n1 + N]) > 0)
                         & (np.abs(np.delete(G, [N, n1 + N], axis=1)).sum(axis=1) == 0))[0]
         A2 = G[poly][:, [N, n1 + N]]
-        d2, _ = qp_solve(np.eye(2), np.zeros(2), A2, h[poly])
+        d2, _ = qp_solve(np.eye(2), -np.asarray(foot, np.float64), A2, h[poly])
         fixed[N], fixed[n1 + N] = d2
     for i in empty:
         if i > 0:
@@ -363,7 +368,7 @@ def herdt_step(cfg, x_init, y_init, v_ref, x_fc, y_fc, current, window, foot_sid
     (x_next (3,), y_next (3,), first_x_footstep or None, first_y_footstep or None)."""
     Q, p, G, h, N, m = herdt_qp(cfg, x_init, y_init, v_ref, x_fc, y_fc, current, window,
                                 foot_side)
-    u, _ = herdt_solve(Q, p, G, h, N, m)
+    u, _ = herdt_solve(Q, p, G, h, N, m, (float(x_fc), float(y_fc)))
     A, B, _ = lipm(cfg.dt, cfg.h, cfg.g)
     n1 = N + m
     xs = A @ np.asarray(x_init, np.float64).reshape(3) + B[:, 0] * u[0]
