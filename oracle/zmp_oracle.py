@@ -150,11 +150,15 @@ def strict_matrices(N, dt, h, g, Q, R):
 
 
 def kkt_check(H, q, z, lo, hi, scale=1.0):
-    """KKT residuals of min ½zᵀHz + qᵀz, lo ≤ z ≤ hi.  Returns dict of maxima."""
+    """KKT residuals of min ½zᵀHz + qᵀz, lo ≤ z ≤ hi.  Returns dict of maxima.
+
+    A slot with hi − lo ≤ 0 is an equality: its multiplier is free in sign, so it enters
+    `primal` only — neither dual term, nor `stationarity`."""
     gr = H @ z + q
-    at_hi = z >= hi - 1e-12
-    at_lo = z <= lo + 1e-12
-    free = ~(at_hi | at_lo)
+    eq = hi - lo <= 0
+    at_hi = (z >= hi - 1e-12) & ~eq
+    at_lo = (z <= lo + 1e-12) & ~eq
+    free = ~(at_hi | at_lo | eq)
     return dict(
         primal=max(0.0, float(np.max(z - hi)), float(np.max(lo - z))),
         stationarity=float(np.max(np.abs(gr[free]))) / scale if free.any() else 0.0,
@@ -166,11 +170,16 @@ def kkt_check(H, q, z, lo, hi, scale=1.0):
 def solve_box_qp(H, q, lo, hi, W0=None, maxit=1000):
     """Exact primal active-set solve of min ½zᵀHz + qᵀz s.t. lo ≤ z ≤ hi (H SPD).
 
-    W0: optional warm-start working set (int8 array: 0 free, 1 at hi, 2 at lo).
+    W0: optional warm-start working set (int8 array: 0 free, 1 at hi, 2 at lo).  Slots with
+    hi − lo ≤ 0 are equalities: in the working set from the start and never dropped.
     Returns (z, working set).
     """
     n = len(q)
     Wset = np.zeros(n, np.int8) if W0 is None else np.asarray(W0, np.int8).copy()
+    # a slot of zero width is an equality: always in the working set, never dropped (its
+    # multiplier may take either sign)
+    eq = hi - lo <= 0
+    Wset[eq & (Wset == 0)] = 1
     # feasible start consistent with the working set: EQP for W0, then clip (clipped slots
     # join the working set)
     F = Wset == 0
@@ -210,6 +219,7 @@ def solve_box_qp(H, q, lo, hi, W0=None, maxit=1000):
         gr = H @ z + q
         # optimal if gr <= 0 at hi-active and gr >= 0 at lo-active
         viol = np.where(Wset == 1, gr, np.where(Wset == 2, -gr, 0.0))
+        viol[eq] = 0.0
         j = int(np.argmax(viol))
         if viol[j] <= 1e-15 * max(1.0, float(np.abs(gr).max())):
             return z, Wset
