@@ -241,7 +241,7 @@ inline UncChoice choose_unc(int N, int64_t n, bool shared_cop, int opt_rollout_k
   const bool generic = opt_rollout_kernel == 1;
   const size_t lds_axis = lds - (size_t)g.kcp * sizeof(double);  // no staged gain row
   size_t lds_split = std::max<size_t>(lds_axis, hist_doubles(g.cw, (int)n) * sizeof(double));
-  // the sparse-difference correlation stages the plan's suffix sums behind the z_ref areas
+  // the sparse-difference correlation stages the plan's suffix sums in front of the z_ref areas
   const size_t lds_sparse = std::max(lds_axis + (size_t)ksum_rows(N) * sizeof(double), lds_split);
   const bool sparse = want_sparse && lds_sparse <= 64 * 1024;
   if (sparse) lds_split = lds_sparse;

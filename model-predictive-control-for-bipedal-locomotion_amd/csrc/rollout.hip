@@ -124,6 +124,15 @@ template <int CW>
 struct ZrLayout {
   static constexpr int kPad = (CW % 2 == 0) ? 1 : 0;
   __host__ __device__ static constexpr int idx(int t) { return t + kPad * (t / CW); }
+  // idx of a runtime row 0 ≤ t < 32768 (the split kernels: two areas of lzp doubles within
+  // 64 KiB).  CW = 6 is the one width whose t / CW is no shift: ⌊t·10923 / 2^16⌋ = ⌊t / 6⌋ below
+  // 2^16 / (6·10923 − 2^16) = 32768, a 24-bit multiply instead of the quarter-rate v_mul_hi.
+  __device__ static __forceinline__ int idx_row(int t) {
+    if constexpr (CW == 6)
+      return t + (int)(__umul24((unsigned)t, 10923u) >> 16);
+    else
+      return idx(t);
+  }
 };
 
 // History staging of the split kernels: row 0 the initial state, row m + 1 the state after
@@ -510,16 +519,18 @@ struct AxisBounds {
 template <int CW>
 __device__ __forceinline__ void axis_load(const RolloutArgs& a, int64_t b, int tid,
                                           AxisBounds<CW>& r) {
-  const double2* zmx = reinterpret_cast<const double2*>(a.zmax + b * a.bstride);
-  const double2* zmn = reinterpret_cast<const double2*>(a.zmin + b * a.bstride);
+  // The walk's two rows as wave-uniform bases (scalar registers) and one 32-bit byte offset per
+  // round that both arrays share: `global_load v, v_off, s[base]`, no 64-bit address per load.
+  const char* zmx = reinterpret_cast<const char*>(a.zmax + b * a.bstride);
+  const char* zmn = reinterpret_cast<const char*>(a.zmin + b * a.bstride);
+  const unsigned last = (unsigned)(a.n - 1) * 16u;
 #pragma unroll
   for (int u = 0; u < AxisBounds<CW>::PF2; ++u) {
-    const int t = u * 128 + tid;
     // clamped rather than predicated (predicated double2 loads here crash the gfx950 backend
     // of ROCm 7.2 in machine copy propagation); dbg bit 8 turns every load into row 0
-    const int tc = dbgb(a, 8) ? 0 : min(t, a.n - 1);
-    r.hi[u] = zmx[tc];
-    r.lo[u] = zmn[tc];
+    const unsigned off = dbgb(a, 8) ? 0u : min((unsigned)(u * 128 + tid) * 16u, last);
+    r.hi[u] = *reinterpret_cast<const double2*>(zmx + off);
+    r.lo[u] = *reinterpret_cast<const double2*>(zmn + off);
   }
 }
 
@@ -644,6 +655,8 @@ __device__ __forceinline__ bool axis_correlate_sparse(const RolloutArgs& a, cons
   const double S0 = Ts[ksum_s0(N)];
 #pragma unroll
   for (int r = 0; r < CW; ++r) f[r] = S0 * gv[r + 1];
+  // the table offset in bytes: the lane's s scaled once per walk
+  const unsigned s8 = (unsigned)s * 8u, e8max = (unsigned)(N + CW - 1) * 8u;
 #pragma unroll
   for (int q = 0; q < CW; ++q) {
     unsigned long long m = mk[q];
@@ -652,8 +665,12 @@ __device__ __forceinline__ bool axis_correlate_sparse(const RolloutArgs& a, cons
       m &= m - 1;
       const double dv = readlane_f64(d[q], L);
       // f_{s+r} += S_{e−r} d with e = m − s, S_{e−r} = Ts[e − r + 8]
-      const int e = min(max(L * CW + q - s, 0), N + CW - 1);
-      const double* p = Ts + e + 9 - CW;
+      // One unsigned minimum clamps both sides: a change before the lane's chunk (e < 0) wraps
+      // to a large offset and lands on e = N + CW − 1 with a change out of reach ahead, where the
+      // CW entries read are the table's upper zeros, as its lower zeros are at e = 0.
+      const unsigned e8 = min(__umul24((unsigned)L, CW * 8u) + (q * 8u - s8), e8max);
+      const double* p = reinterpret_cast<const double*>(reinterpret_cast<const char*>(Ts) + e8) +
+                        (9 - CW);
 #pragma unroll
       for (int r = 0; r < CW; ++r) f[r] = fma(p[CW - 1 - r], dv, f[r]);
     }
@@ -696,7 +713,8 @@ __device__ __forceinline__ void split_walk(const RolloutArgs& a, int64_t b, doub
   // partial counts, and the walk's own data is one memory round trip away.  Order: x0 and kick,
   // the bounds, the last sample (wave-uniform: scalar loads), the table rows.
   if constexpr (PM && !SHF) __builtin_amdgcn_s_setprio(3);  // issue the walk's loads first
-  const double* xb = a.x0 + b * 6 + 3 * axis;
+  const double* xb = reinterpret_cast<const double*>(reinterpret_cast<const char*>(a.x0 + b * 6) +
+                                                     (unsigned)axis * 24u);
   const double xi[3] = {xb[0], xb[1], xb[2]};
   const double kks = (a.kick != nullptr) ? a.kick[b] : 0.0;  // wave-uniform: a scalar load
   if constexpr (SHF) {
@@ -713,8 +731,9 @@ __device__ __forceinline__ void split_walk(const RolloutArgs& a, int64_t b, doub
     {
       const double* tp = a.ksum != nullptr ? a.ksum : kg;
       const int tl = a.ksum != nullptr ? ksum_rows(a.hN) - 1 : 0;
-      ts0 = tp[min(tid, tl)];
-      ts1 = tp[min(tid + 128, tl)];
+      const char* tb = reinterpret_cast<const char*>(tp);  // uniform base, 32-bit byte offsets
+      ts0 = *reinterpret_cast<const double*>(tb + min((unsigned)tid, (unsigned)tl) * 8u);
+      ts1 = *reinterpret_cast<const double*>(tb + min((unsigned)tid + 128u, (unsigned)tl) * 8u);
     }
   }
   if constexpr (PM && !SHF) __builtin_amdgcn_s_setprio(0);
@@ -730,9 +749,12 @@ __device__ __forceinline__ void split_walk(const RolloutArgs& a, int64_t b, doub
   const double ek[3] = {ekp[0], ekp[1], ekp[2]};
   const double kk = (kicked && lane == kl) ? kks : 0.0;  // the kick on its lane, +0.0 elsewhere
   if constexpr (!SHF) {
-    double* zr0 = smem;
+    // the suffix-sum table first, at the workgroup's fixed LDS base (the sparse correlation's
+    // table reads add a constant to their clamped offset, not the runtime 2·lzp), the two z_ref
+    // areas behind it
+    double* Ts = smem;
+    double* zr0 = smem + (a.ksum != nullptr ? ksum_rows(a.hN) : 0);
     double* zr1 = zr0 + a.lzp;
-    double* Ts = smem + 2 * a.lzp;  // the suffix-sum table behind the two z_ref areas
     // ---- 2. z_ref rows + window padding (zmp_controller.py:81-88), table rows ----------------
     // Branch-free, so that the bound loads stay up front (under `if (t < n)` the compiler sinks
     // a round's loads into the branch, behind a full drain): a thread past the walk's end holds
@@ -741,14 +763,14 @@ __device__ __forceinline__ void split_walk(const RolloutArgs& a, int64_t b, doub
 #pragma unroll
     for (int u = 0; u < AxisBounds<CW>::PF2; ++u) {
       const int t = min(u * 128 + tid, a.lz - 1);
-      zr0[ZL::idx(t)] = (r.hi[u].x + r.lo[u].x) / 2;
-      zr1[ZL::idx(t)] = (r.hi[u].y + r.lo[u].y) / 2;
+      zr0[ZL::idx_row(t)] = (r.hi[u].x + r.lo[u].x) / 2;
+      zr1[ZL::idx_row(t)] = (r.hi[u].y + r.lo[u].y) / 2;
     }
     {
       const double l0 = (hl.x + ll.x) / 2, l1 = (hl.y + ll.y) / 2;
       for (int t = kRows + tid; t < a.lz; t += 128) {
-        zr0[ZL::idx(t)] = l0;
-        zr1[ZL::idx(t)] = l1;
+        zr0[ZL::idx_row(t)] = l0;
+        zr1[ZL::idx_row(t)] = l1;
       }
     }
     if (a.ksum != nullptr) {
@@ -785,10 +807,12 @@ __device__ __forceinline__ void split_walk(const RolloutArgs& a, int64_t b, doub
     // sat before the first barrier behind a runtime branch and the table loop's drain, so every
     // first-round wave waited for them before its correlation (27.0–27.3 µs).
     if constexpr (PFB) {
-      const double* src = (tid < 64 ? a.zmax : a.zmin) + min(b + a.pf_ahead, a.B - 1) * a.bstride;
-      const int ln = tid & 63, nd = 2 * n;
-      pf0 = src[min(ln * 8, nd - 1)];
-      pf1 = src[min(ln * 8 + 512, nd - 1)];
+      // (the array by wave on the scalar unit: a uniform base and 32-bit byte offsets, as axis_load)
+      const char* src = reinterpret_cast<const char*>((ywave ? a.zmin : a.zmax) +
+                                                      min(b + a.pf_ahead, a.B - 1) * a.bstride);
+      const unsigned l64 = (unsigned)lane * 64u, endb = (unsigned)(2 * n - 1) * 8u;
+      pf0 = *reinterpret_cast<const double*>(src + min(l64, endb));
+      pf1 = *reinterpret_cast<const double*>(src + min(l64 + 4096u, endb));
     }
   }
   // ---- 4. lane-chunk affine scan -----------------------------------------------------------
@@ -840,15 +864,19 @@ __device__ __forceinline__ void split_walk(const RolloutArgs& a, int64_t b, doub
   // kick: a scalar compare per step): kk is the kick on lane kl and +0.0 on every other lane,
   // which changes no value.  (A second copy of the replay without the test, taken by waves
   // without a kick, cost the shared-CoP kernel 2 %: config 4 unconstrained 495 vs 486 µs.)
+  // The lane's CW staging rows are 48 B apart behind one address: rows l·CW + 1 .. l·CW + CW lie
+  // in the pad span (l·CW + q) / (2·CW) = l / 2 for every q < CW (HistLayout::row).
+  double* orow = stage + (mbeg + 1) * 6 + HistLayout<CW>::kPad * (lane >> 1) + 3 * axis;
+  static_assert(HistLayout<CW>::kSpan == 2 * CW, "a lane's rows share one pad span");
+  const int live = nsteps - mbeg;  // the lane's steps q < live exist (one compare per step)
 #pragma unroll
   for (int q = 0; q < CW; ++q) {
-    const int m = mbeg + q;
-    if (m < nsteps) {
+    if (q < live) {
       const double u = f[q] - (kx0 * x[0] + kx1 * x[1] + kx2 * x[2]);
       double xn[3];
       lipm_step(lc, x, u, xn);
       if (q == qk) xn[1] -= kk;  // force kick (zmp_controller.py:90,105-106)
-      double* o = stage + HistLayout<CW>::row(m + 1) + 3 * axis;
+      double* o = orow + 6 * q;
       o[0] = xn[0];
       o[1] = xn[1];
       o[2] = xn[2];
