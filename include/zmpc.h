@@ -231,6 +231,33 @@ int zmpc_walk_metrics(const zmpc_plan* plan, int64_t B, int64_t n, const double*
                       const int64_t* lengths, double* metrics, void* stream);
 
 /*
+ * Rollout and walk metrics in one launch: the reference's F_ext sweep plus the look at the plot
+ * (run_compare_resistance.py:87-197 — :87-169 walks every force, :173-197 draws each ZMP against
+ * its support boxes) as one call that keeps twelve doubles per walk and never materialises the
+ * [B, n, 2, 3] state history.  `metrics` holds what zmpc_walk_metrics returns for the history
+ * that zmpc_rollout (kick_steps NULL) / zmpc_rollout_kicks would write for the same arguments:
+ * the same slots, the same sample-i-against-bounds-row-i rule, the same clamp of `lengths`, the
+ * same non-finite rule, the same uncontracted z, box centre and v.  Value slots agree with that
+ * pair of launches to rounding (1e-11 on O(1) states; the kernels' instruction streams differ),
+ * so a count or an index may differ where a sample sits within rounding of its bound.
+ *   zmax, zmin, bounds_stride, x0, kick, kick_step : as zmpc_rollout
+ *   kick_steps : [B] int64 or NULL  per-walk kick steps as zmpc_rollout_kicks; NULL: kick_step
+ *   lengths    : [B] int64 or NULL  live samples per walk, as zmpc_walk_metrics.  Every walk is
+ *                                   still rolled out over all n samples (status covers them)
+ *   metrics    : [B, ZMPC_NMETRICS] as zmpc_walk_metrics
+ *   status     : [B] or NULL        what the rollout writes
+ * The reductions run in an order fixed by the lane numbers: two calls on the same input agree bit
+ * for bit.  Takes the walks the split kernels roll out: a non-strict plan, n − 1 <= 512 steps (one
+ * correlation pass) within 64 KiB of LDS, ZMPC_OPT_ROLLOUT_KERNEL = 0; ZMPC_OPT_CORRELATION is
+ * honoured.  Strict plans and every other shape return ZMPC_ESTATE with the reason and launch
+ * nothing: use zmpc_rollout + zmpc_walk_metrics there.  Additive to ABI 7.
+ */
+int zmpc_rollout_metrics(const zmpc_plan* plan, int64_t B, int64_t n, const double* zmax,
+                         const double* zmin, int64_t bounds_stride, const double* x0,
+                         const double* kick, int64_t kick_step, const int64_t* kick_steps,
+                         const int64_t* lengths, double* metrics, int32_t* status, void* stream);
+
+/*
  * Batched CoP-bound producer: CoPGenerator.generate_cop_trajectory
  * (generators/cop_generator.py:34-115) over the footstep plan of
  * generators/footstep_generator.py:19-49, one walk per set of parameters.

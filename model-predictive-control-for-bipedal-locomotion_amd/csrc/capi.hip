@@ -401,6 +401,39 @@ int zmpc_walk_metrics(const zmpc_plan* P, int64_t B, int64_t n, const double* hi
   return ZMPC_OK;
 }
 
+int zmpc_rollout_metrics(const zmpc_plan* P, int64_t B, int64_t n, const double* zmax,
+                         const double* zmin, int64_t bounds_stride, const double* x0,
+                         const double* kick, int64_t kick_step, const int64_t* kick_steps,
+                         const int64_t* lengths, double* metrics, int32_t* status, void* stream) {
+  g_err.clear();
+  if (!P) return fail(ZMPC_EINVAL, "NULL plan");
+  if (B < 0 || n < 1) return fail(ZMPC_EINVAL, "need B >= 0 and n >= 1");
+  if (bounds_stride != 0 && bounds_stride < 2 * n)
+    return fail(ZMPC_EINVAL, "bounds_stride must be 0 (shared CoP) or >= 2n");
+  if (B > 0 && (!zmax || !zmin || !x0 || !metrics))
+    return fail(ZMPC_EINVAL, "NULL array argument");
+  if (B > 0x7fffffff) return fail(ZMPC_EINVAL, "batch too large");
+  if (n > (1 << 24)) return fail(ZMPC_EINVAL, "walk too long");
+  // the shapes without a fused form: refused before any device call, nothing is launched
+  if (P->strict)
+    return fail(ZMPC_ESTATE, "zmpc_rollout_metrics: strict plans have no fused form (use "
+                             "zmpc_rollout + zmpc_walk_metrics)");
+  const MetChoice c = choose_unc_metrics(P->N, n, bounds_stride == 0,
+                                         P->opt[ZMPC_OPT_ROLLOUT_KERNEL],
+                                         P->opt[ZMPC_OPT_CORRELATION]);
+  if (c.kind == MetKind::None)
+    return fail(ZMPC_ESTATE, std::string("zmpc_rollout_metrics: ") + c.why +
+                                 " (use zmpc_rollout + zmpc_walk_metrics)");
+  if (B == 0) return ZMPC_OK;
+  DeviceGuard g(P->device);
+  if (g.err != hipSuccess) return hip_fail(g.err, "hipSetDevice");
+  const RolloutCall rc{B, n, zmax, zmin, bounds_stride, x0, kick, kick_step, kick_steps, nullptr,
+                       status};
+  const hipError_t e =
+      zmpc_launch_rollout_metrics(P, rc, lengths, metrics, (hipStream_t)stream);
+  return launch_result(e, std::string(), "zmpc_rollout_metrics");
+}
+
 static int herdt_check(const zmpc_plan* P, const zmpc_herdt_params* prm, int64_t B) {
   if (!P || !prm) return fail(ZMPC_EINVAL, "NULL plan or params");
   if (B < 0) return fail(ZMPC_EINVAL, "B < 0");

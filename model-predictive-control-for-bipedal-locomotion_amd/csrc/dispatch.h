@@ -264,6 +264,79 @@ inline UncChoice choose_unc(int N, int64_t n, bool shared_cop, int opt_rollout_k
   return c;
 }
 
+// The fused rollout-to-metrics launch (zmpc_rollout_metrics; rollout.hip split_walk with MET):
+// the split kernels' walk with the replay feeding the metrics reduction instead of a history.
+//   Sample0      n = 1 (choose_unc: Copy): the metrics of x0 alone, zmpc_metrics_x0_kernel;
+//   Split        zmpc_rollout_metrics_splitd_kernel<CW, false>, where choose_unc answers Split;
+//   SplitShared  zmpc_shared_f_kernel, then zmpc_rollout_metrics_splitd_kernel<CW, true>, where
+//                choose_unc answers SplitShared;
+//   None         every other shape (Generic, Wide, Chunk): no fused form, `why` names the reason.
+// CW, the geometry fields and the sparse attempt are choose_unc's, so the fused walk takes the
+// history walk's arithmetic up to the replay.  The LDS holds no history staging: the z_ref areas
+// (with the suffix sums in front), reused after the correlation for the walk's bounds — per axis
+// one (z_max, z_min) pair of doubles per sample in the z_ref row layout, from which each lane
+// reads the rows of its own CW samples.
+enum class MetKind { None, Sample0, Split, SplitShared };
+
+// Doubles of the bounds staging: two axes of 16-byte (z_max, z_min) pairs, rows as ZrLayout
+// (one pad row per cw rows for even cw).
+constexpr size_t metrics_bound_doubles(int cw, int n) {
+  return 4 * (size_t)(n + ((cw % 2 == 0) ? (n - 1) / cw : 0));
+}
+
+struct MetChoice {
+  MetKind kind;
+  const char* why;  // None: the reason, for the caller's message
+  int cw;
+  bool sparse;
+  size_t lds;
+  int kc, kcp, lz, lzp, kfm;
+  int fstride;  // SplitShared: doubles per axis of the precomputed f, 0 otherwise
+};
+
+inline MetChoice choose_unc_metrics(int N, int64_t n, bool shared_cop, int opt_rollout_kernel,
+                                    int opt_correlation) {
+  MetChoice m{};
+  if (opt_rollout_kernel == 1) {
+    m.why = "the one-wave cross-check kernel (rollout kernel option 1) has no fused form";
+    return m;
+  }
+  // (the long-walk option only chooses among the forms of walks that take several passes)
+  const UncChoice c = choose_unc(N, n, shared_cop, opt_rollout_kernel, 0, opt_correlation);
+  switch (c.kind) {
+    case UncKind::Copy:
+      m.kind = MetKind::Sample0;
+      return m;
+    case UncKind::Split:
+    case UncKind::SplitShared:
+      break;
+    case UncKind::Generic:
+      m.why = "the horizon's split-kernel LDS passes 64 KiB (one-wave kernel): no fused form";
+      return m;
+    default:
+      m.why = "walks of more than 513 samples (wide and chunk kernels) have no fused form";
+      return m;
+  }
+  m.kind = c.kind == UncKind::Split ? MetKind::Split : MetKind::SplitShared;
+  m.cw = c.cw;
+  m.sparse = c.sparse;
+  m.kc = c.kc;
+  m.kcp = c.kcp;
+  m.lz = c.lz;
+  m.lzp = c.lzp;
+  m.kfm = c.kfm;
+  m.fstride = c.fstride;
+  const size_t bounds = metrics_bound_doubles(c.cw, (int)n) * sizeof(double);
+  m.lds = bounds;
+  if (m.kind == MetKind::Split)
+    m.lds = std::max(bounds, ((size_t)2 * c.lzp + (c.sparse ? ksum_rows(N) : 0)) * sizeof(double));
+  if (m.lds > 64 * 1024) {  // (cannot happen where choose_unc's own 64 KiB rule passed)
+    m = MetChoice{};
+    m.why = "the fused form's LDS passes 64 KiB";
+  }
+  return m;
+}
+
 // ---------------------------------------------------------------------------------------------
 // Strict box-QP (strict_dispatch.hip and its backends)
 

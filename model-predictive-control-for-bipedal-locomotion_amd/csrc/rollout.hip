@@ -678,6 +678,86 @@ __device__ __forceinline__ bool axis_correlate_sparse(const RolloutArgs& a, cons
   return true;
 }
 
+// ---- fused rollout-to-metrics (zmpc_rollout_metrics) ------------------------------------------
+// What the metrics form of split_walk needs beside RolloutArgs.
+struct MetArgs {
+  double* metrics;         // [B, ZMPC_NMETRICS]
+  const int64_t* lengths;  // [B] live samples per walk, or null: n
+  double hg, sqrt_hg;      // h/g and its root (plan)
+};
+
+// One lane's share of one axis of the walk metrics, and the butterfly that combines the 64 lanes:
+// the quantities, the strict comparisons, the tie rule and the uncontracted arithmetic of
+// metrics.hip AxisAcc (include/zmpc.h zmpc_walk_metrics), here fed from the replay's registers.
+struct MetAcc {
+  double vmax = 0.0;     // largest violation so far
+  int vidx = -1;         // its first sample, −1 while vmax is 0
+  int count = 0;         // samples with a violation
+  double dev = 0.0;      // largest |c − zr|
+  double sq = 0.0;       // Σ (z − zr)²
+  int bad = 0x7fffffff;  // first sample with a non-finite state value
+
+  __device__ __forceinline__ void add(int i, double c, double v, double a, double hi, double lo,
+                                      double hg) {
+#pragma clang fp contract(off)
+    if (!(isfinite(c) && isfinite(v) && isfinite(a))) {
+      bad = min(bad, i);
+      return;
+    }
+    const double z = c - hg * a;
+    const double zr = (hi + lo) * 0.5;
+    const double viol = fmax(fmax(z - hi, lo - z), 0.0);
+    if (viol > 0.0) ++count;
+    if (viol > vmax) {  // strict: a lane's samples ascend, the first one that attains it stays
+      vmax = viol;
+      vidx = i;
+    }
+    dev = fmax(dev, fabs(c - zr));
+    const double d = z - zr;
+    sq += d * d;
+  }
+
+  // c + ċ·sqrt(h/g) − zr of one sample (dcm_end)
+  __device__ static __forceinline__ double dcm(double c, double v, double hi, double lo,
+                                               double sqrt_hg) {
+#pragma clang fp contract(off)
+    return c + v * sqrt_hg - (hi + lo) * 0.5;
+  }
+
+  // xor butterfly over the wave: symmetric in the two lanes, so every lane ends with the same
+  // bits in an order fixed by the lane numbers; a tie in the violation goes to the lower index
+  __device__ __forceinline__ void reduce() {
+#pragma unroll
+    for (int mask = 1; mask < 64; mask <<= 1) {
+      const double ov = __shfl_xor(vmax, mask);
+      const int oi = __shfl_xor(vidx, mask);
+      if (ov > vmax || (ov == vmax && oi < vidx)) {
+        vmax = ov;
+        vidx = oi;
+      }
+      count += __shfl_xor(count, mask);
+      dev = fmax(dev, __shfl_xor(dev, mask));
+      sq += __shfl_xor(sq, mask);
+      bad = min(bad, __shfl_xor(bad, mask));
+    }
+  }
+
+  // slot k (viol_max, viol_argmax, viol_count, com_dev_max, zmp_rms, dcm_end) of the axis
+  __device__ __forceinline__ double slot(int k, int nb, double dcm_end) const {
+#pragma clang fp contract(off)
+    if (bad != 0x7fffffff)  // fail safe, as metrics.hip
+      return k == 0 ? __builtin_inf() : (k == 1 ? (double)bad : __builtin_nan(""));
+    switch (k) {
+      case 0: return vmax;
+      case 1: return (double)vidx;
+      case 2: return (double)count;
+      case 3: return dev;
+      case 4: return sqrt(sq / (double)nb);
+      default: return dcm_end;
+    }
+  }
+};
+
 // Split-axis kernel, one walk per 128-thread workgroup: wave 0 solves the x axis and wave 1 the
 // y axis (half the registers and twice the waves of the one-wave kernel, for latency hiding);
 // they share the staged z_ref and the history staging rows, so loads and stores stay whole-walk
@@ -687,16 +767,23 @@ __device__ __forceinline__ bool axis_correlate_sparse(const RolloutArgs& a, cons
 // three barriers per walk.  The tables read on wave-uniform addresses come in as __restrict__
 // pointers so the compiler keeps them on scalar loads even inside a loop that stores the history.
 // SHF: shared CoP, f precomputed once per launch (zmpc_shared_f_kernel).
+// MET (zmpc_rollout_metrics): phases 1–4 as they are; the replay feeds each state to the walk
+// metrics instead of a history row, the two waves' six numbers leave as one 96-byte row, and no
+// history exists (hist is null).  The bounds registers of phase 1 stay alive over the correlation
+// and go into the dead z_ref area as (z_max, z_min) pairs per axis, where each lane finds the rows
+// of its own samples: the metrics see the bounds themselves, not z_ref ± a half width.
 // PM (the persistent kernel): the walk's global loads and its history copy-out are issued at
 // raised wave priority, so a CU's co-resident walks get their memory traffic out ahead of the
 // others' correlation (config 2: 45.3 → 43.8 µs; the one-walk-per-workgroup grid is not helped).
 // FFA: odd chunk widths take the two-parallel fast-FIR form of the dense correlation.
-template <int CW, bool SHF, bool PM, bool FFA, bool PFB>
+template <int CW, bool SHF, bool PM, bool FFA, bool PFB, bool MET = false>
 __device__ __forceinline__ void split_walk(const RolloutArgs& a, int64_t b, double* smem,
                                            int* flag, const double* __restrict__ kg,
                                            const double* __restrict__ scanP,
                                            const double* __restrict__ kxp,
-                                           double* __restrict__ hist) {
+                                           double* __restrict__ hist,
+                                           const MetArgs& mo = MetArgs{},
+                                           double* mrow = nullptr) {
   using ZL = ZrLayout<CW>;
   const int tid = threadIdx.x, lane = tid & 63, axis = tid >> 6;
   const int n = a.n, nsteps = n - 1;
@@ -722,6 +809,7 @@ __device__ __forceinline__ void split_walk(const RolloutArgs& a, int64_t b, doub
     const double* fp = a.fsh + axis * a.fstride + lane * CW;
 #pragma unroll
     for (int q = 0; q < CW; ++q) f[q] = fp[q];
+    if constexpr (MET) axis_load<CW>(a, b, tid, r);  // the one CoP (stride 0), from the caches
   } else {
     axis_load<CW>(a, b, tid, r);
     hl = reinterpret_cast<const double2*>(a.zmax + b * a.bstride)[n - 1];
@@ -815,6 +903,22 @@ __device__ __forceinline__ void split_walk(const RolloutArgs& a, int64_t b, doub
       pf1 = *reinterpret_cast<const double*>(src + min(l64 + 4096u, endb));
     }
   }
+  // ---- (MET) the walk's bounds into the dead z_ref area ------------------------------------
+  // axis a's pairs (z_max, z_min) of sample t at double2 row a·nbp + ZrLayout row(t); the barrier
+  // that publishes them is the one before the replay, so the scan runs in between
+  const int nbp = n + ZL::kPad * ((n - 1) / CW);
+  if constexpr (MET) {
+    double2* bb = reinterpret_cast<double2*>(smem);
+#pragma unroll
+    for (int u = 0; u < AxisBounds<CW>::PF2; ++u) {
+      const int t = u * 128 + tid;
+      if (t < n) {
+        const int row = ZL::idx_row(t);
+        bb[row] = make_double2(r.hi[u].x, r.lo[u].x);
+        bb[nbp + row] = make_double2(r.hi[u].y, r.lo[u].y);
+      }
+    }
+  }
   // ---- 4. lane-chunk affine scan -----------------------------------------------------------
   const LipmConsts lc = a.lc;
   const double kx0 = kxp[0], kx1 = kxp[1], kx2 = kxp[2];
@@ -852,6 +956,55 @@ __device__ __forceinline__ void split_walk(const RolloutArgs& a, int64_t b, doub
   for (int i = 0; i < 3; ++i) {
     const double p = dpp_f64<0x138, 0xF>(sv[i]);  // wave_shr:1
     x[i] = (lane == 0) ? xi[i] : p;
+  }
+  if constexpr (MET) {
+    // ---- 5m. replay (reference form) into the walk metrics ---------------------------------
+    // Lane l owns samples l·CW + 1 .. l·CW + CW (the states its steps produce), lane 0 also
+    // sample 0; only samples below the walk's live length n_b count.  The rollout itself runs all
+    // n − 1 steps: the status is the history launch's.
+    int64_t nbl = mo.lengths != nullptr ? mo.lengths[b] : (int64_t)n;  // wave-uniform
+    nbl = nbl < 1 ? 1 : (nbl > n ? n : nbl);
+    const int nb = (int)nbl;
+    __syncthreads();  // the staged bounds
+    const double2* bl = reinterpret_cast<const double2*>(smem) + axis * nbp + lane * (CW + ZL::kPad);
+    MetAcc acc;
+    double dcm = 0.0;  // of the lane that owns sample n_b − 1
+    if (lane == 0) {
+      const double2 bd = bl[0];
+      acc.add(0, xi[0], xi[1], xi[2], bd.x, bd.y, mo.hg);
+      if (nb == 1) dcm = MetAcc::dcm(xi[0], xi[1], bd.x, bd.y, mo.sqrt_hg);
+    }
+    const int live = nsteps - mbeg;
+#pragma unroll
+    for (int q = 0; q < CW; ++q) {
+      if (q < live) {
+        const double u = f[q] - (kx0 * x[0] + kx1 * x[1] + kx2 * x[2]);
+        double xn[3];
+        lipm_step(lc, x, u, xn);
+        if (q == qk) xn[1] -= kk;  // force kick (zmp_controller.py:90,105-106)
+        const int i = mbeg + q + 1;
+        if (i < nb) {
+          const double2 bd = bl[ZL::idx(1 + q)];
+          acc.add(i, xn[0], xn[1], xn[2], bd.x, bd.y, mo.hg);
+          if (i == nb - 1) dcm = MetAcc::dcm(xn[0], xn[1], bd.x, bd.y, mo.sqrt_hg);
+        }
+#pragma unroll
+        for (int i2 = 0; i2 < 3; ++i2) x[i2] = xn[i2];
+      }
+    }
+    acc.reduce();
+    const int owner = __builtin_amdgcn_readfirstlane(nb >= 2 ? (nb - 2) / CW : 0);
+    const double dcm_end = readlane_f64(dcm, owner);
+    const bool finite = isfinite(x[0]) && isfinite(x[1]) && isfinite(x[2]);
+    const unsigned long long badx = __ballot(!finite);
+    if (lane == 0) flag[axis] = badx ? ZMPC_ST_NONFINITE : 0;
+    // slot 2k + a: the two waves' six numbers interleave into one row
+    if (lane < 6) mrow[2 * lane + axis] = acc.slot(lane, nb, dcm_end);
+    __syncthreads();
+    if (tid < ZMPC_NMETRICS) mo.metrics[b * ZMPC_NMETRICS + tid] = mrow[tid];
+    if (a.status != nullptr && tid == 0) a.status[b] = flag[0] | flag[1];
+    if (a.dbg < 0) mo.metrics[tid] = pf0 + pf1;  // never (dbg ≥ 0): keeps the prefetch loads
+    return;
   }
   // ---- 5. replay (reference form) straight into the staged history ------------------------
   double* stage = smem;
@@ -977,6 +1130,37 @@ __global__ void __launch_bounds__(128, 4) zmpc_rollout_unc_splitd_kernel(Rollout
   __shared__ int flag[2];
   split_walk<CW, SHF, false, true, PFB>(a, blockIdx.x, smem, flag, (CW & 1) ? a.kffa : a.k,
                                         a.scanP, a.kx, a.hist);
+}
+
+// The fused rollout-to-metrics kernels: the walk of zmpc_rollout_unc_splitd_kernel<CW, SHF>
+// with the metrics replay (split_walk MET), one walk per 128-thread workgroup; no next-round
+// prefetch (launch_metrics).
+template <int CW, bool SHF>
+__global__ void __launch_bounds__(128, 4)
+    zmpc_rollout_metrics_splitd_kernel(RolloutArgs a, MetArgs mo) {
+  extern __shared__ __attribute__((aligned(16))) double smem[];
+  __shared__ int flag[2];
+  __shared__ double mrow[ZMPC_NMETRICS];
+  split_walk<CW, SHF, false, true, false, true>(a, blockIdx.x, smem, flag,
+                                                (CW & 1) ? a.kffa : a.k, a.scanP, a.kx, nullptr, mo,
+                                                mrow);
+}
+
+// n = 1: the metrics of the initial state alone (the rollout is a copy of x0, status 0); one
+// thread per walk and axis through the same accumulator.
+__global__ void __launch_bounds__(256) zmpc_metrics_x0_kernel(RolloutArgs a, MetArgs mo) {
+  const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (e >= 2 * a.B) return;
+  const int64_t b = e >> 1;
+  const int axis = (int)(e & 1);
+  const double* x = a.x0 + b * 6 + 3 * axis;
+  const double hi = a.zmax[b * a.bstride + axis], lo = a.zmin[b * a.bstride + axis];
+  MetAcc acc;
+  acc.add(0, x[0], x[1], x[2], hi, lo, mo.hg);
+  const double dcm_end = MetAcc::dcm(x[0], x[1], hi, lo, mo.sqrt_hg);
+#pragma unroll
+  for (int k = 0; k < 6; ++k) mo.metrics[b * ZMPC_NMETRICS + 2 * k + axis] = acc.slot(k, 1, dcm_end);
+  if (a.status != nullptr && axis == 0) a.status[b] = 0;
 }
 
 // ---- FFT correlation (long walks) ------------------------------------------------------------
@@ -1939,6 +2123,92 @@ hipError_t zmpc_launch_rollout_unc(const zmpc_plan* p, const RolloutCall& rc, hi
 #ifdef ZMPC_DIAG
   tl_write(a.tl, rc.B, s, e);
 #endif
+  if (fsh) {
+    const hipError_t ef = hipFreeAsync(fsh, s);
+    if (e == hipSuccess) e = ef;
+  }
+  return e;
+}
+
+namespace {
+
+// The fused launch at tile width CW, per-walk bounds or the shared form.  No next-round prefetch:
+// at config 2 the fused launch ran 28.0–28.3 µs without it and 30.9–31.1 µs with it under the
+// history launcher's rule (diagnostics build, three alternations, profiles/r9/fused/prefetch_ab.txt)
+// — without the history staging ten workgroups fit a CU instead of eight, the batch takes fewer
+// dispatch rounds, and the touched lines mostly compete with the walks' own loads.
+template <int CW>
+void launch_metrics(const MetChoice& c, hipStream_t s, const RolloutArgs& a, const MetArgs& mo) {
+  if (c.kind == MetKind::SplitShared)
+    hipLaunchKernelGGL((zmpc_rollout_metrics_splitd_kernel<CW, true>), dim3((unsigned)a.B),
+                       dim3(128), c.lds, s, a, mo);
+  else
+    hipLaunchKernelGGL((zmpc_rollout_metrics_splitd_kernel<CW, false>), dim3((unsigned)a.B),
+                       dim3(128), c.lds, s, a, mo);
+}
+
+}  // namespace
+
+// zmpc_rollout_metrics: the kernel by dispatch.h choose_unc_metrics (the caller has refused the
+// shapes it does not take), then the launch.  rc.hist is unused.
+hipError_t zmpc_launch_rollout_metrics(const zmpc_plan* p, const RolloutCall& rc,
+                                       const int64_t* lengths, double* metrics, hipStream_t s) {
+  const MetChoice c = choose_unc_metrics(p->N, rc.n, rc.bstride == 0,
+                                         p->opt[ZMPC_OPT_ROLLOUT_KERNEL],
+                                         p->opt[ZMPC_OPT_CORRELATION]);
+  if (c.kind == MetKind::None) return hipErrorInvalidValue;
+  RolloutArgs a{};
+  a.kc = c.kc;
+  a.kcp = c.kcp;
+  a.lz = c.lz;
+  a.lzp = c.lzp;
+  a.n = (int)rc.n;
+  a.B = rc.B;
+  a.lc = p->lc;
+  a.k = p->k;
+  a.kx = p->kx;
+  a.zmax = rc.zmax;
+  a.zmin = rc.zmin;
+  a.bstride = rc.bstride;
+  a.x0 = rc.x0;
+  a.kick = rc.kick;
+  a.kick_step = rc.kick_step;
+  a.status = rc.status;
+  a.scanP = p->scanP;
+  a.kick_steps = rc.kick_steps;
+  a.kffa = p->kffa;
+  a.kfm = c.kfm;
+  a.ksum = c.sparse ? p->ksum : nullptr;
+  a.hN = p->N;
+  a.fstride = c.fstride;
+  const MetArgs mo{metrics, lengths, p->hg, sqrt(p->hg)};
+  if (c.kind == MetKind::Sample0) {
+    hipLaunchKernelGGL(zmpc_metrics_x0_kernel, dim3((unsigned)((2 * rc.B + 255) / 256)), dim3(256),
+                       0, s, a, mo);
+    return hipGetLastError();
+  }
+  double* fsh = nullptr;  // SplitShared: f of the shared CoP, once per launch
+  if (c.kind == MetKind::SplitShared) {
+    if (hipMallocAsync((void**)&fsh, 2 * (size_t)c.fstride * sizeof(double), s) != hipSuccess) {
+      (void)hipGetLastError();
+      return hipErrorOutOfMemory;
+    }
+    hipLaunchKernelGGL(zmpc_shared_f_kernel, dim3((unsigned)((c.fstride + 255) / 256), 2),
+                       dim3(256), 0, s, rc.zmax, rc.zmin, (int)rc.n, p->k, c.kc, fsh, c.fstride);
+    a.fsh = fsh;
+  }
+  hipError_t e = hipSuccess;
+  switch (c.cw) {
+#define ZMPC_CW(C)                              \
+  case C:                                       \
+    launch_metrics<C>(c, s, a, mo);             \
+    break;
+    ZMPC_CW(1) ZMPC_CW(2) ZMPC_CW(3) ZMPC_CW(4) ZMPC_CW(5) ZMPC_CW(6) ZMPC_CW(7) ZMPC_CW(8)
+#undef ZMPC_CW
+    default:
+      e = hipErrorInvalidValue;
+  }
+  if (e == hipSuccess) e = hipGetLastError();
   if (fsh) {
     const hipError_t ef = hipFreeAsync(fsh, s);
     if (e == hipSuccess) e = ef;

@@ -121,6 +121,11 @@ hipError_t zmpc_launch_rollout_unc(const zmpc_plan* p, const RolloutCall& c, hip
                                    std::string* why);
 hipError_t zmpc_launch_step_unc(const zmpc_plan* p, const StepCall& c, hipStream_t s);
 
+// fused rollout-to-metrics (rollout.hip): the shapes dispatch.h choose_unc_metrics takes (the
+// caller refuses the others first); c.hist is unused, lengths may be NULL
+hipError_t zmpc_launch_rollout_metrics(const zmpc_plan* p, const RolloutCall& c,
+                                       const int64_t* lengths, double* metrics, hipStream_t s);
+
 // strict box-QP rollout / step: the solver of the launch by dispatch.h choose_strict, then its
 // backend below (strict_dispatch.hip)
 hipError_t zmpc_launch_rollout_strict(const zmpc_plan* p, const RolloutCall& c, hipStream_t s,

@@ -70,6 +70,10 @@ SIGNATURES = {
     "zmpc_walk_metrics": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64,
                                          _c_dbl_p, _c_dbl_p, _c_dbl_p, ctypes.c_int64,
                                          ctypes.c_void_p, _c_dbl_p, ctypes.c_void_p]),
+    "zmpc_rollout_metrics": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64,
+                                            _c_dbl_p, _c_dbl_p, ctypes.c_int64, _c_dbl_p, _c_dbl_p,
+                                            ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p,
+                                            _c_dbl_p, ctypes.c_void_p, ctypes.c_void_p]),
     "zmpc_cop_generate": (ctypes.c_int, [ctypes.c_int, ctypes.c_int64, _c_dbl_p, ctypes.c_int64,
                                          _c_dbl_p, _c_dbl_p, ctypes.c_void_p, ctypes.c_void_p,
                                          ctypes.c_void_p]),

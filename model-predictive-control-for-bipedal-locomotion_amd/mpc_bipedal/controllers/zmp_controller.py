@@ -255,6 +255,15 @@ class ZMPController:
                 walk and hist[b, :n_b] is walk b's history
         Returns (hist [B,n,2,3], status [B]) on the plan's device.
         """
+        plan, zmax_t, x0, kick, step = self._batch_inputs(x_init, z_max, F_ext, force_step,
+                                                          walk_lengths)
+        hist, st = plan.rollout(zmax_t, z_min, x0, kick=kick, kick_step=step)
+        if plan.strict:
+            self._raise_on_status(st)
+        return hist, st
+
+    def _batch_inputs(self, x_init, z_max, F_ext, force_step, walk_lengths):
+        """Device inputs of the batch methods: (plan, z_max, x0, kick, kick step(s))."""
         plan = self._plan()
         dev = torch.device("cuda", plan.device)
         zmax_t = torch.as_tensor(z_max, dtype=torch.float64, device=dev)
@@ -273,10 +282,23 @@ class ZMPController:
             step = torch.as_tensor(walk_lengths, dtype=torch.int64, device=dev).reshape(B) // 2
         else:
             step = (n // 2) if force_step is None else int(force_step)
-        hist, st = plan.rollout(zmax_t, z_min, x0, kick=kick, kick_step=step)
+        return plan, zmax_t, x0, kick, step
+
+    def generate_walk_metrics_batch(self, x_init, z_max, z_min, F_ext=None,
+                                    force_step: Optional[int] = None, walk_lengths=None):
+        """The walks of generate_state_trajectory_batch (same arguments) reduced to their
+        robustness metrics in one launch (addition; zmpc_rollout_metrics): what walk_metrics
+        returns for that method's history, which is never written — 96 bytes per walk leave the
+        device's registers instead of n·48.  With walk_lengths the metrics cover each walk's own
+        n_b samples.  Returns (analysis.WalkMetrics, status [B]) on the plan's device.  Strict
+        plans and walks of more than 513 samples run the two launches behind the same call."""
+        plan, zmax_t, x0, kick, step = self._batch_inputs(x_init, z_max, F_ext, force_step,
+                                                          walk_lengths)
+        m, st = plan.rollout_metrics(zmax_t, z_min, x0, kick=kick, kick_step=step,
+                                     lengths=walk_lengths)
         if plan.strict:
             self._raise_on_status(st)
-        return hist, st
+        return WalkMetrics(m), st
 
     def generate_com_trajectory_batch(self, x_init, z_max, z_min, F_ext=None,
                                       force_step: Optional[int] = None, walk_lengths=None):
@@ -310,7 +332,8 @@ class ZMPController:
     def critical_force(self, z_max, z_min, x_init=None, force_step=None, direction=+1,
                        F_hi: float = 1000.0, iters: int = 30, max_violation: float = 1e-9,
                        max_com_dev: Optional[float] = None,
-                       max_dcm_end: Optional[float] = None, walk_lengths=None):
+                       max_dcm_end: Optional[float] = None, walk_lengths=None,
+                       fused: bool = False):
         """Largest push each scenario survives (addition): the question the F_ext sweep of
         run_compare_resistance.py:87-169 puts to the eye, answered by bisection on the device.
 
@@ -322,7 +345,12 @@ class ZMPController:
         |dcm_end| <= max_dcm_end (and, on a strict plan, the solver reported no failure).
         Bisection on F in [0, F_hi]: each of the iters + 2 evaluations is one batched rollout
         into one reused history buffer, one walk_metrics launch and a torch.where on the
-        bracket; nothing is copied to the host.
+        bracket; nothing is copied to the host.  With fused=True each evaluation is one
+        zmpc_rollout_metrics launch into the reused [B,12] tensor and no history buffer exists
+        (B·n·48 bytes less on the device: 20 GB against 96 MB of metrics for a million 420-sample
+        scenarios); it needs a shape with a fused form (Plan.rollout_metrics) and raises
+        otherwise.  Its value slots agree with the two launches to rounding, so a bracket can
+        differ where a push lands a sample within rounding of max_violation.
 
         Returns (F_lo, F_hi), [B] device tensors: the final bracket, F_lo passes and F_hi fails,
         F_hi − F_lo = F_hi/2**iters.  NaN in both where the walk fails with no push at all;
@@ -363,15 +391,20 @@ class ZMPController:
         else:
             step = torch.as_tensor(force_step, dtype=torch.int64, device=dev)
         kick = torch.zeros(B, **f64)
-        launch = plan.rollout_launcher(zmax_t, zmin_t, x0, kick=kick, kick_step=step)
         metrics = torch.empty((B, NMETRICS), **f64)
+        if fused:
+            launch = plan.rollout_metrics_launcher(zmax_t, zmin_t, x0, kick=kick, kick_step=step,
+                                                   lengths=lengths, out=metrics)
+        else:
+            launch = plan.rollout_launcher(zmax_t, zmin_t, x0, kick=kick, kick_step=step)
         m = WalkMetrics(metrics)
         dt, mass = self.config.dt, self.config.m
 
         def passes(F):
             kick.copy_(dt * (sign * F) / mass)  # zmp_controller.py:106
             launch()
-            plan.walk_metrics(launch.hist, zmax_t, zmin_t, lengths=lengths, out=metrics)
+            if not fused:
+                plan.walk_metrics(launch.hist, zmax_t, zmin_t, lengths=lengths, out=metrics)
             ok = (m.viol_max <= max_violation).all(dim=1)  # (+inf and NaN fail)
             if max_com_dev is not None:
                 ok &= (m.com_dev_max <= max_com_dev).all(dim=1)

@@ -182,13 +182,8 @@ class Plan:
         _native.check(rc, name)
         return hist, status
 
-    def _rollout_args(self, zmax, zmin, x0, kick, kick_step, hist, status):
-        """Batched Wieber rollout → hist [B,n,2,3] (device), status [B].
-
-        zmax/zmin: [B,n,2] per-walk CoP bounds, or [n,2] one CoP shared by every walk;
-        x0: [B,2,3]; kick: [B] velocity impulse subtracted from y at step kick_step — an int,
-        or a [B] array of per-walk steps (ragged walks: zmpc_rollout_kicks).
-        """
+    def _walk_inputs(self, zmax, zmin, x0):
+        """The walks of a rollout on the device: (zmax, zmin, x0, B, n, bounds stride)."""
         zmax = self._as_dev(zmax)
         x0 = self._as_dev(x0)
         if x0.dim() != 3 or x0.shape[1:] != (2, 3):
@@ -204,6 +199,16 @@ class Plan:
             bstride = 2 * n
         else:
             raise ValueError(f"z_max must be [B, n, 2] or [n, 2], got {tuple(zmax.shape)}")
+        return zmax, zmin, x0, B, n, bstride
+
+    def _rollout_args(self, zmax, zmin, x0, kick, kick_step, hist, status):
+        """Batched Wieber rollout → hist [B,n,2,3] (device), status [B].
+
+        zmax/zmin: [B,n,2] per-walk CoP bounds, or [n,2] one CoP shared by every walk;
+        x0: [B,2,3]; kick: [B] velocity impulse subtracted from y at step kick_step — an int,
+        or a [B] array of per-walk steps (ragged walks: zmpc_rollout_kicks).
+        """
+        zmax, zmin, x0, B, n, bstride = self._walk_inputs(zmax, zmin, x0)
         kick_t = None if kick is None else self._as_dev(kick, (B,))
         if hist is None:
             hist = torch.empty((B, n, 2, 3), dtype=torch.float64, device=self._dev())
@@ -269,6 +274,79 @@ class Plan:
                                                   ctypes.c_void_p(stream))
         _native.check(rc, "zmpc_walk_metrics")
         return out
+
+    # -- fused rollout-to-metrics (zmpc_rollout_metrics) -----------------------------------
+    def _rollout_metrics_args(self, zmax, zmin, x0, kick, kick_step, lengths, out, status):
+        dev = self._dev()
+        zmax, zmin, x0, B, n, bstride = self._walk_inputs(zmax, zmin, x0)
+        kick_t = None if kick is None else self._as_dev(kick, (B,))
+        if isinstance(kick_step, (int, np.integer)):
+            step, ks = int(kick_step), None
+        else:
+            step = -1
+            ks = torch.as_tensor(kick_step, dtype=torch.int64, device=dev).contiguous()
+            if tuple(ks.shape) != (B,):
+                raise ValueError(f"per-walk kick_step must be [B], got {tuple(ks.shape)}")
+        len_t = None
+        if lengths is not None:
+            len_t = torch.as_tensor(lengths, dtype=torch.int64, device=dev).contiguous()
+            if tuple(len_t.shape) != (B,):
+                raise ValueError(f"lengths must be [B] = [{B}], got {tuple(len_t.shape)}")
+        if out is None:
+            out = torch.empty((B, _native.NMETRICS), dtype=torch.float64, device=dev)
+        elif tuple(out.shape) != (B, _native.NMETRICS) or out.dtype != torch.float64 or \
+                out.device != dev or not out.is_contiguous():
+            raise ValueError(f"out must be a contiguous float64 [B, {_native.NMETRICS}] tensor "
+                             "on the plan's device")
+        if status is None:
+            status = torch.empty(B, dtype=torch.int32, device=dev)
+        args = (self._live(), B, n, _ptr(zmax), _ptr(zmin), bstride, _ptr(x0), _ptr(kick_t), step,
+                _ptr(ks), _ptr(len_t), _ptr(out), _ptr(status))
+        return out, status, args, (zmax, zmin, x0, kick_t, ks, len_t)
+
+    def rollout_metrics_launcher(self, zmax, zmin, x0, kick=None, kick_step=-1, lengths=None,
+                                 out=None, status=None):
+        """rollout_launcher's counterpart for the fused launch: validate once and return a
+        zero-argument callable that re-issues zmpc_rollout_metrics on the current stream
+        (launch.metrics, launch.status are its outputs).  Fused only: a shape without a fused
+        form raises NativeError at the first call."""
+        out, status, args, keep = self._rollout_metrics_args(zmax, zmin, x0, kick, kick_step,
+                                                             lengths, out, status)
+        fn = _native.load().zmpc_rollout_metrics
+        dev = self.device
+
+        def launch():
+            stream = torch.cuda.current_stream(dev).cuda_stream
+            rc = fn(*args, ctypes.c_void_p(stream))
+            if rc != 0:
+                _native.check(rc, "zmpc_rollout_metrics")
+        launch.metrics, launch.status, launch.inputs = out, status, keep
+        return launch
+
+    def rollout_metrics(self, zmax, zmin, x0, kick=None, kick_step=-1, lengths=None, out=None,
+                        status=None, fused_only=False):
+        """Batched Wieber rollout reduced to the walk metrics in one launch
+        (zmpc_rollout_metrics): (metrics [B,12], status [B]) on the device, what walk_metrics
+        returns for rollout's history of the same arguments, with no [B,n,2,3] history in between.
+
+        Arguments as rollout (zmax/zmin [B,n,2] or a shared [n,2]; x0 [B,2,3]; kick [B];
+        kick_step an int or a [B] array of per-walk steps) and walk_metrics (lengths [B] or None;
+        out a [B,12] tensor to write into).  Where the library has no fused form — strict plans,
+        walks of more than 513 samples, the one-wave cross-check kernel — it answers ZMPC_ESTATE
+        and this method runs rollout + walk_metrics instead (the same figures, with the history as
+        a temporary); fused_only=True raises NativeError there."""
+        out, status, args, keep = self._rollout_metrics_args(zmax, zmin, x0, kick, kick_step,
+                                                             lengths, out, status)
+        with torch.cuda.device(self.device):
+            stream = torch.cuda.current_stream(self.device).cuda_stream
+            rc = _native.load().zmpc_rollout_metrics(*args, ctypes.c_void_p(stream))
+        if rc == _native.ZMPC_ESTATE and not fused_only:
+            zmax_t, zmin_t, x0_t, kick_t, _, len_t = keep
+            hist, status = self.rollout(zmax_t, zmin_t, x0_t, kick=kick_t, kick_step=kick_step,
+                                        status=status)
+            return self.walk_metrics(hist, zmax_t, zmin_t, lengths=len_t, out=out), status
+        _native.check(rc, "zmpc_rollout_metrics")
+        return out, status
 
     # -- Herdt joint footstep QP (zmpc_herdt_rollout / zmpc_herdt_step) --------------------
     def herdt_rollout(self, params, v_ref, states, nb_next, x0, kick=None, kick_step=-1):
