@@ -2,8 +2,8 @@
 // dynamic LDS, a call of a given shape takes.  Plain host C++17 — integers and option values in,
 // POD structs out; no HIP call, no plan pointer, no environment, no allocation — so that the
 // rules compile and run without a GPU (tests/test_dispatch_host.py pins them).  The launchers
-// (rollout.hip, strict_dispatch.hip, strict_lq.hip, strict_scan.hip, capi.hip) ask here and only
-// launch; the device code reads the layout constants below.
+// (rollout.hip with rollout_long.hip, strict_dispatch.hip, strict_lq.hip, strict_scan.hip,
+// capi.hip) ask here and only launch; the device code reads the layout constants below.
 #pragma once
 
 #include <algorithm>
@@ -25,7 +25,7 @@ constexpr int kFftPmin = 256;   // smallest transform with a gain spectrum
 constexpr int kFftGComplex = 2 * kFftPT - kFftPmin;  // Σ_P P over P = kFftPmin..kFftPT
 
 // ---------------------------------------------------------------------------------------------
-// Unconstrained rollout (rollout.hip)
+// Unconstrained rollout (rollout.hip; the wide and chunk kernels: rollout_long.hip)
 
 // Correlation tile width: outputs per lane per pass, chosen per walk length so that
 // passes·64·CW barely covers the n−1 timesteps (n = 420 → CW = 7: 448 outputs, 1 pass).
@@ -42,7 +42,7 @@ inline int pick_cw(int64_t nsteps) {
   return best;
 }
 
-// Doubles of the split kernels' history staging for n rows at tile width cw (rollout.hip
+// Doubles of the split kernels' history staging for n rows at tile width cw (rollout_common.h
 // HistLayout: two pad doubles after every 2·cw step rows for even cw).
 constexpr size_t hist_doubles(int cw, int n) {
   return (size_t)n * 6 + (size_t)((cw % 2 == 0) ? 2 : 0) * ((n + 2 * cw - 1) / (2 * cw));
@@ -152,17 +152,22 @@ inline size_t chunk_lds_bytes(const ChunkGeom& g) {
 //   Chunk        any length: zmpc_rollout_unc_chunk_kernel<8>, one wave per walk.
 enum class UncKind { Copy, SplitShared, Split, Generic, Wide, Chunk };
 
-struct UncChoice {
-  UncKind kind;
+// What a choice puts into the kernel arguments (rollout_common.h RolloutArgs), shared by the
+// history launch and the fused rollout-to-metrics launch.
+struct WalkGeom {
   int cw;       // correlation tile width (the kernel's CW), 0 for Copy
+  bool sparse;  // the kernel stages the plan's suffix sums and tries the sparse-difference
+                // correlation first (the split and wide kernels only)
+  int kc, kcp, lz, lzp, kfm;  // geometry fields of the kernel arguments
+  int fstride;  // SplitShared: doubles per axis of the precomputed f, 0 otherwise
+};
+
+struct UncChoice : WalkGeom {
+  UncKind kind;
   int w;        // Wide: waves per axis (2, 4 or 8), 0 otherwise
   int E, P;     // Wide with the FFT correlation: points per thread (4 or 8) and transform size;
                 // 0, 0 for the direct form and every other kind
-  bool sparse;  // the kernel stages the plan's suffix sums and tries the sparse-difference
-                // correlation first (the split and wide kernels only)
   size_t lds;   // dynamic LDS bytes of the launch
-  int kc, kcp, lz, lzp, kfm;  // geometry fields of the kernel arguments (RolloutArgs)
-  int fstride;  // SplitShared: doubles per axis of the precomputed f, 0 otherwise
   int lc;       // Chunk: timesteps per chunk, 0 otherwise
 };
 
@@ -284,14 +289,10 @@ constexpr size_t metrics_bound_doubles(int cw, int n) {
   return 4 * (size_t)(n + ((cw % 2 == 0) ? (n - 1) / cw : 0));
 }
 
-struct MetChoice {
+struct MetChoice : WalkGeom {
   MetKind kind;
   const char* why;  // None: the reason, for the caller's message
-  int cw;
-  bool sparse;
   size_t lds;
-  int kc, kcp, lz, lzp, kfm;
-  int fstride;  // SplitShared: doubles per axis of the precomputed f, 0 otherwise
 };
 
 inline MetChoice choose_unc_metrics(int N, int64_t n, bool shared_cop, int opt_rollout_kernel,
@@ -318,14 +319,7 @@ inline MetChoice choose_unc_metrics(int N, int64_t n, bool shared_cop, int opt_r
       return m;
   }
   m.kind = c.kind == UncKind::Split ? MetKind::Split : MetKind::SplitShared;
-  m.cw = c.cw;
-  m.sparse = c.sparse;
-  m.kc = c.kc;
-  m.kcp = c.kcp;
-  m.lz = c.lz;
-  m.lzp = c.lzp;
-  m.kfm = c.kfm;
-  m.fstride = c.fstride;
+  static_cast<WalkGeom&>(m) = c;
   const size_t bounds = metrics_bound_doubles(c.cw, (int)n) * sizeof(double);
   m.lds = bounds;
   if (m.kind == MetKind::Split)

@@ -497,7 +497,7 @@ static void launch_gram(int N, Op op, double alpha, double diag, double* C, hipS
   }
 }
 
-// FFT tables (rollout.hip, long walks): twiddles e^{−2πi m/PT}, m < PT (sincospi: the
+// FFT tables (rollout_long.hip, long walks): twiddles e^{−2πi m/PT}, m < PT (sincospi: the
 // argument −2m/PT is exact), and for every P = 2^p in [kFftPmin, PT] the gain spectrum
 // DFT(g)[q]/P, g[d] = k_{d−1} for d = 1..N (the correlation f_i = Σ_d g[d] z_{i+d}), summed
 // directly with exact table angles ((q·d) mod P).

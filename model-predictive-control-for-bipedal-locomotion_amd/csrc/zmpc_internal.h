@@ -16,7 +16,7 @@
 constexpr int kScanLevels = 7;
 constexpr int kScanStride = kScanLevels * 9;
 // ... followed by the per-lane powers (Ā^C)^k, k = 0..32, [8][33][9] (the DPP scan's cross-row
-// steps, rollout.hip scan_dpp)
+// steps, rollout_common.h scan_dpp)
 constexpr int kScanPowOff = 8 * kScanStride;
 // ... and the chunk-sum columns Ā^p B, Ā^p e1 (p = 0..7), [8][6] (rollout.hip split_walk: a
 // lane's chunk end state Σ_q Ā^(C−1−q) B f_q, and the kick's Ā^(C−1−q) e1)
@@ -61,7 +61,7 @@ struct zmpc_plan {
   // strict LQ solver (strict_lq.hip): free-tail Riccati table [N][16] and work counters
   double* lqtab = nullptr;
   unsigned long long* lqcnt = nullptr;  // [ZMPC_NCOUNTERS]
-  // FFT correlation of long unconstrained walks (rollout.hip): twiddles e^{−2πi m/PT}
+  // FFT correlation of long unconstrained walks (rollout_long.hip): twiddles e^{−2πi m/PT}
   // [PT] complex, and per transform size P = 2^p in [kFftPmin, PT] the spectrum of the
   // gain kernel g[d] = k_{d−1} (d = 1..N), DFT(g)/P, at complex offset P − kFftPmin
   double* fft_tw = nullptr;
@@ -120,6 +120,13 @@ hipError_t zmpc_launch_walk_metrics(const zmpc_plan* p, int64_t B, int64_t n, co
 hipError_t zmpc_launch_rollout_unc(const zmpc_plan* p, const RolloutCall& c, hipStream_t s,
                                    std::string* why);
 hipError_t zmpc_launch_step_unc(const zmpc_plan* p, const StepCall& c, hipStream_t s);
+
+// the wide and chunk kernels of long walks (rollout_long.hip), for zmpc_launch_rollout_unc and
+// zmpc_rollout_unc_set_attrs alone: the launch of a Wide or Chunk choice with the caller's filled
+// RolloutArgs (rollout_common.h; the struct is local to each unit, hence the untyped pointer)
+hipError_t zmpc_launch_rollout_long(const UncChoice& c, const void* rollout_args, int cus,
+                                    hipStream_t s);
+hipError_t zmpc_rollout_long_set_attrs();
 
 // fused rollout-to-metrics (rollout.hip): the shapes dispatch.h choose_unc_metrics takes (the
 // caller refuses the others first); c.hist is unused, lengths may be NULL
