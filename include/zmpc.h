@@ -78,7 +78,18 @@ int zmpc_plan_destroy(zmpc_plan* plan);
  * what: 0 = p (N), 1 = Px (N*3, row-major), 2 = M (N*N), 3 = gain k (N), 4 = kx (3),
  *       5 = G (N*N, strict plans only), 6 = Cholesky factor L of M (N*N, lower),
  *       7 = Hz = Q·I + R·Pu⁻ᵀPu⁻¹ = G⁻¹ (N*N, strict plans only).
- * count = number of doubles dst can hold; must be >= the quantity's size. */
+ * The derived tables the kernels read (additive to ABI 7; layouts as csrc/zmpc_internal.h and
+ * csrc/dispatch.h document them):
+ *       8 = fast-FIR taps of k ((N + 2)/2 + 8 rows of 4: E_m, O_m, E_m + O_{m−1}, 0),
+ *       9 = suffix sums of k (N + 18: S_{i−8} at 9 <= i <= N + 7, S_0 at N + 16, zero elsewhere),
+ *       10 = rollout scan tables (2928: [8][7][9] (Ā^C)^(2^r), then [8][33][9] (Ā^C)^k, then
+ *            [8][6] (Ā^p·B, Ā^p·e1)),
+ *       11 = X = L⁻¹·Puᵀ (N*N, strict plans only), 12 = v = first column of Pu⁻¹ (N, strict
+ *            plans only),
+ *       13 = FFT twiddles e^{−2πi m/8192} (2*8192, re/im interleaved), 14 = gain spectra
+ *            DFT(g)/P for P = 256, 512, .., 8192 at complex offset P − 256 (2*16128).
+ * count = number of doubles dst can hold; must be >= the quantity's size.  A quantity the plan
+ * does not hold returns ZMPC_ESTATE, an unknown id or a short destination ZMPC_EINVAL. */
 int zmpc_plan_export(const zmpc_plan* plan, int32_t what, double* dst_host, int64_t count);
 
 /*
@@ -111,7 +122,9 @@ int zmpc_plan_counters(const zmpc_plan* plan, uint64_t* dst_host, int32_t count,
  *   [2] Cholesky M = L·Lᵀ (blocked)  [3] gain row k, kx (two triangular solves)
  *   [4] rollout scan propagators     [5] FFT correlation tables
  *   [6] strict: X = L⁻¹·Puᵀ          [7] strict: G = XᵀX / Q (FP64 MFMA Gram)
- *   [8] strict: v = Pu⁻¹·e0          [9] strict: Hz = Q·I + R·VᵀV (FP64 MFMA Gram)
+ *   [8] strict: v = Pu⁻¹·e0          [9] strict: Hz = Q·I + R·VᵀV (FP64 MFMA Gram), Hz's own
+ *                                        Cholesky factor and, where its pivots spread less than
+ *                                        M's, G again as Hz⁻¹ from that factor
  *   [10] strict: LQ free-tail table  [11] total
  * Stages a plan does not run read 0.  count = floats dst can hold (at most ZMPC_PLAN_STAGES
  * are written).

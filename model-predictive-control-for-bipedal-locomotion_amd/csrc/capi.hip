@@ -286,6 +286,13 @@ int zmpc_plan_export(const zmpc_plan* P, int32_t what, double* dst, int64_t coun
     case 5: src = P->G; n = P->G ? N * N : 0; break;
     case 6: src = P->L; n = N * N; break;
     case 7: src = P->Hz; n = P->Hz ? N * N : 0; break;
+    case 8: src = P->kffa; n = 4 * (int64_t)kffa_rows((int)N); break;
+    case 9: src = P->ksum; n = ksum_rows((int)N); break;
+    case 10: src = P->scanP; n = kScanDoubles; break;
+    case 11: src = P->X; n = P->X ? N * N : 0; break;
+    case 12: src = P->v; n = P->v ? N : 0; break;
+    case 13: src = P->fft_tw; n = 2 * (int64_t)kFftPT; break;
+    case 14: src = P->fft_g; n = 2 * (int64_t)kFftGComplex; break;
     default: return fail(ZMPC_EINVAL, "unknown export id");
   }
   if (!src || n == 0) return fail(ZMPC_ESTATE, "quantity not held by this plan");

@@ -8,8 +8,14 @@
 //   3. M = L Lᵀ (blocked Cholesky, 16-column panels, FP64 MFMA panel updates)
 //   4. y = M⁻¹ e0, gain row k = Pu y (= row 0 of inv(M) Puᵀ), kx = k·Px
 //   5. strict plans: X = L⁻¹ Puᵀ, G = XᵀX / Q = Pu (R·I + Q·PuᵀPu)⁻¹ Puᵀ,
-//      the inverse z-space Hessian of the strict QP (zmp_controller.py:173-195).
+//      the inverse z-space Hessian of the strict QP (zmp_controller.py:173-195); where Hz, the
+//      Hessian itself, is the better conditioned of the two, G = Hz⁻¹ from Hz's own factor
+//      (regain_G).
 #include "zmpc_internal.h"
+
+#include <math.h>
+
+#include <vector>
 
 typedef double dbl4 __attribute__((ext_vector_type(4)));
 
@@ -530,6 +536,77 @@ __global__ void zmpc_fft_gain(int N, const double* __restrict__ k, const double*
   g[2 * idx + 1] = im / P;
 }
 
+// Spread of a Cholesky factor's pivots, max L_ii / min L_ii: its square bounds the factored
+// matrix's condition number from below.  The diagonal is copied to the host (synchronises s).
+// +inf for a factor with a non-positive or non-finite pivot.
+static hipError_t pivot_spread(const double* L, int N, hipStream_t s, double* spread) {
+  std::vector<double> d((size_t)N);
+  hipError_t e = hipMemcpy2DAsync(d.data(), sizeof(double), L, ((size_t)N + 1) * sizeof(double),
+                                  sizeof(double), (size_t)N, hipMemcpyDeviceToHost, s);
+  if (e != hipSuccess) return e;
+  if ((e = hipStreamSynchronize(s)) != hipSuccess) return e;
+  double lo = INFINITY, hi = 0.0;
+  bool ok = true;
+  for (double x : d) {
+    ok = ok && x > 0.0 && x < INFINITY;
+    lo = fmin(lo, x);
+    hi = fmax(hi, x);
+  }
+  *spread = ok ? hi / lo : INFINITY;
+  return hipSuccess;
+}
+
+// 5c. G again, by the better conditioned of its two routes.  G = XᵀX/Q goes through the Cholesky
+// factor of M = PuᵀPu + (R/Q)·I and loses cond(M)·u; G = Hz⁻¹ through the factor of
+// Hz = Q·I + R·Pu⁻ᵀPu⁻¹ loses cond(Hz)·u, and cond(M)·cond(Hz) = cond(PuᵀPu): a small R/Q makes M
+// the ill-conditioned one (N = 129, Q = 1, R = 1e-9: G = XᵀX/Q was 1.7e-12 from the true G, relative
+// to its largest entry, where np.linalg.inv(Hz) is 6e-16), a large R/Q makes Hz (R = 1e-2: 7e-16
+// against 3e-12).  So Hz is factored too (the same panel kernel, its factor in G's own buffer),
+// and where its pivots spread less than M's, G = Hz⁻¹ = WᵀW with W = Lh⁻¹ (the same blocked
+// forward substitution, from the identity, in a scratch matrix freed before returning).  X stays
+// L⁻¹·Puᵀ either way.
+static hipError_t regain_G(zmpc_plan* P, hipStream_t s) {
+  const int N = P->N;
+  const size_t nn = (size_t)N * N;
+  double spread_m = 0.0, spread_h = 0.0;
+  hipError_t e = pivot_spread(P->L, N, s, &spread_m);
+  if (e != hipSuccess) return e;
+  double* W = nullptr;  // [N,N], then one int: the status of Hz's factorisation
+  if ((e = hipMalloc((void**)&W, (nn + 1) * sizeof(double))) != hipSuccess) return e;
+  int* info = (int*)(W + nn);
+  const std::vector<double> ones((size_t)N, 1.0);  // outlives the copy below: freed after hipFree
+  auto run = [&]() -> hipError_t {
+    hipError_t r;
+    // the first G stays in place while Hz's factor takes shape in the scratch matrix
+    if ((r = hipMemsetAsync(info, 0, sizeof(double), s)) != hipSuccess) return r;
+    for (int p0 = 0; p0 < N; p0 += 16) {
+      hipLaunchKernelGGL(zmpc_chol_panel, dim3((N - p0 + 15) / 16), dim3(64), 0, s, N, p0, P->Hz,
+                         W, info);
+      if ((r = hipGetLastError()) != hipSuccess) return r;
+    }
+    if ((r = pivot_spread(W, N, s, &spread_h)) != hipSuccess) return r;
+    if (!(spread_h < spread_m)) return hipSuccess;
+    // Lh moves to G's buffer (G is rebuilt from W alone), W becomes the identity, then Lh⁻¹
+    if ((r = hipMemcpyAsync(P->G, W, nn * sizeof(double), hipMemcpyDeviceToDevice, s)) !=
+        hipSuccess)
+      return r;
+    if ((r = hipMemsetAsync(W, 0, nn * sizeof(double), s)) != hipSuccess) return r;
+    if ((r = hipMemcpy2DAsync(W, ((size_t)N + 1) * sizeof(double), ones.data(), sizeof(double),
+                              sizeof(double), (size_t)N, hipMemcpyHostToDevice, s)) != hipSuccess)
+      return r;
+    for (int r0 = 0; r0 < N; r0 += 16) {
+      hipLaunchKernelGGL(zmpc_trsm_panel, dim3((N + 15) / 16), dim3(64), 0, s, N, r0, P->G, W);
+      if ((r = hipGetLastError()) != hipSuccess) return r;
+    }
+    launch_gram(N, DenseOp{W, N}, 1.0, 0.0, P->G, s);
+    if ((r = hipGetLastError()) != hipSuccess) return r;
+    return hipStreamSynchronize(s);  // W is read until here
+  };
+  e = run();
+  const hipError_t f = hipFree(W);
+  return e != hipSuccess ? e : f;
+}
+
 hipError_t zmpc_launch_plan(zmpc_plan* P, hipStream_t s, hipEvent_t* ev) {
   const int N = P->N;
   hipError_t e;
@@ -602,6 +679,7 @@ hipError_t zmpc_launch_plan(zmpc_plan* P, hipStream_t s, hipEvent_t* ev) {
     if ((e = mark(9)) != hipSuccess) return e;
     launch_gram(N, ToeplitzOp{P->v, N}, P->R, P->Q, P->Hz, s);
     if ((e = hipGetLastError()) != hipSuccess) return e;
+    if ((e = regain_G(P, s)) != hipSuccess) return e;
   }
   // stage 10 (the strict LQ table) and the total are recorded by the caller
   return mark(10);

@@ -33,6 +33,22 @@ ST_FACTOR = 4
 ST_INFEASIBLE = 8
 
 EXPORT_P, EXPORT_PX, EXPORT_M, EXPORT_K, EXPORT_KX, EXPORT_G, EXPORT_L, EXPORT_HZ = range(8)
+# the derived tables (additive to ABI 7); X and V on strict plans only
+(EXPORT_KFFA, EXPORT_KSUM, EXPORT_SCAN, EXPORT_X, EXPORT_V, EXPORT_FFT_TW,
+ EXPORT_FFT_G) = range(8, 15)
+# their sizes (csrc/zmpc_internal.h kffa_rows, kScanDoubles; csrc/dispatch.h ksum_rows, kFftPT,
+# kFftPmin, kFftGComplex)
+SCAN_DOUBLES = 2928
+FFT_PT, FFT_PMIN = 8192, 256
+FFT_G_COMPLEX = 2 * FFT_PT - FFT_PMIN
+
+
+def kffa_rows(N: int) -> int:
+    return (N + 2) // 2 + 8
+
+
+def ksum_rows(N: int) -> int:
+    return N + 18
 
 # zmpc_plan_set_option (include/zmpc.h ZMPC_OPT_*): algorithm selection, same solutions
 OPTIONS = {"correlation": 0, "long_walk": 1, "rollout_kernel": 2, "kick_order": 3,

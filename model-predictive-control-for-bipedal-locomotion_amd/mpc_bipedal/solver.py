@@ -78,16 +78,26 @@ class Plan:
             self._h = None
 
     def export(self, what: int) -> np.ndarray:
+        """A plan quantity on the host (zmpc_plan_export, ids _native.EXPORT_*).  Matrices come
+        back [N, N], Px [N, 3], the fast-FIR taps [rows, 4], the FFT tables complex."""
         n = {0: self.N, 1: 3 * self.N, 2: self.N ** 2, 3: self.N, 4: 3, 5: self.N ** 2,
-             6: self.N ** 2, 7: self.N ** 2}[what]
+             6: self.N ** 2, 7: self.N ** 2, 8: 4 * _native.kffa_rows(self.N),
+             9: _native.ksum_rows(self.N), 10: _native.SCAN_DOUBLES, 11: self.N ** 2,
+             12: self.N, 13: 2 * _native.FFT_PT, 14: 2 * _native.FFT_G_COMPLEX}.get(what)
+        if n is None:
+            raise ValueError(f"zmpc_plan_export: unknown export id {what}")
         buf = np.empty(n, dtype=np.float64)
         rc = _native.load().zmpc_plan_export(
             self._live(), what, buf.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), n)
         _native.check(rc, "zmpc_plan_export")
         if what in (1,):
             return buf.reshape(self.N, 3)
-        if what in (2, 5, 6, 7):
+        if what in (2, 5, 6, 7, 11):
             return buf.reshape(self.N, self.N)
+        if what == 8:
+            return buf.reshape(-1, 4)
+        if what in (13, 14):
+            return buf.view(np.complex128)
         return buf
 
     def counters(self, reset: bool = False) -> dict:

@@ -112,14 +112,15 @@ def gain_row(N, dt, h, g, Q, R):
     return k, k @ Px
 
 
-def rollout_gain(zmax, zmin, x0, N, dt, h, g, Q, R, kick=None, kick_step=-1):
-    """Batched unconstrained rollout.  zmax/zmin [B,n,2], x0 [B,2,3], kick [B] (or None).
-    Returns hist [B,n,2,3]."""
+def rollout_gain(zmax, zmin, x0, N, dt, h, g, Q, R, kick=None, kick_step=-1, gain=None):
+    """Batched unconstrained rollout.  zmax/zmin [B,n,2], x0 [B,2,3], kick [B] (or None),
+    kick_step an int or a [B] array of per-walk steps; gain: (k, kx) to roll out with instead of
+    gain_row's (a gain row known to higher precision).  Returns hist [B,n,2,3]."""
     zmax = np.asarray(zmax, np.float64)
     zmin = np.asarray(zmin, np.float64)
     Bn, n = zmax.shape[0], zmax.shape[1]
     A, Bv, _ = lipm(dt, h, g)
-    k, kx = gain_row(N, dt, h, g, Q, R)
+    k, kx = gain_row(N, dt, h, g, Q, R) if gain is None else gain
     zr = (zmax + zmin) / 2
     zr = np.concatenate([zr, np.repeat(zr[:, -1:, :], N, axis=1)], axis=1)   # [B, n+N, 2]
     # f_i = Σ_j k_j z_ref[i+1+j]  for all steps at once
@@ -132,8 +133,12 @@ def rollout_gain(zmax, zmin, x0, N, dt, h, g, Q, R, kick=None, kick_step=-1):
     for i in range(n - 1):
         u = f[:, i, :] - x @ kx                                              # [B, 2]
         x = x @ A.T + u[..., None] * Bv[:, 0]
-        if i == kick_step:
-            x[:, 1, 1] -= kk
+        if np.ndim(kick_step) == 0:
+            if i == kick_step:
+                x[:, 1, 1] -= kk
+        else:
+            hit = np.asarray(kick_step) == i
+            x[hit, 1, 1] -= kk[hit]
         hist[:, i + 1] = x
     return hist
 

@@ -48,15 +48,20 @@ def test_plan_matrices(N):
     Mref = Pu.T @ Pu + R / Q * np.eye(N)
     Md = p.export(_native.EXPORT_M)
     assert np.abs(Md - Mref).max() <= 1e-13 * np.abs(Mref).max()    # MFMA (N>=64) / FMA
+    # The oracle itself is within 8.3e-13 (k), 2.6e-13 (kx), 1.5e-14 (G) and 2.0e-14 (Hz) of a
+    # 60-digit solve at these six cases, relative to each quantity's largest entry;
+    # the device is held to 16 x that against the truth (tests/test_gpu_plan_cases.py), hence to
+    # 17 x that against the oracle.
     k, kx = O.gain_row(N, dt, H, G, Q, R)
-    assert np.abs(p.export(_native.EXPORT_K) - k).max() <= 1e-9 * np.abs(k).max()
+    assert np.abs(p.export(_native.EXPORT_K) - k).max() <= 1.5e-11 * np.abs(k).max()
     assert np.allclose(p.export(_native.EXPORT_KX), kx, rtol=1e-9, atol=0)
+    assert np.abs(p.export(_native.EXPORT_KX) - kx).max() <= 5e-12 * np.abs(kx).max()
     Gd = p.export(_native.EXPORT_G)
     Hz, V, _, _ = O.strict_matrices(N, dt, H, G, Q, R)
     Gref = np.linalg.inv(Hz)
-    assert np.abs(Gd - Gref).max() <= 1e-10 * np.abs(Gref).max()
+    assert np.abs(Gd - Gref).max() <= 3e-13 * np.abs(Gref).max()
     Hd = p.export(_native.EXPORT_HZ)
-    assert np.abs(Hd - Hz).max() <= 1e-10 * np.abs(Hz).max()
+    assert np.abs(Hd - Hz).max() <= 4e-13 * np.abs(Hz).max()
 
 
 @pytest.mark.parametrize("N", (10, 64, 150, 512))
