@@ -271,6 +271,56 @@ int zmpc_rollout_metrics(const zmpc_plan* plan, int64_t B, int64_t n, const doub
                          const int64_t* lengths, double* metrics, int32_t* status, void* stream);
 
 /*
+ * Push-robustness map: the exact largest push every (walk, push step, direction) survives, from
+ * the unpushed state history in one call.  The reference can only sample a few forces at one step
+ * and look (run_compare_resistance.py:87-197); ZMPController.critical_force brackets one step per
+ * scenario with 32 pushed rollouts.  For the unconstrained controller neither is needed: the
+ * closed loop x⁺ = Ā x + B f, Ā = A − B·kxᵀ, is linear and time-invariant, so the y-axis ZMP
+ * response at sample i to a unit push at step s depends on the delay d = i − s alone,
+ *     r_0 = 0,  r_d = −(dt/mass)·C·Ā^(d−1)·e1  (d >= 1),  C = (1, 0, −h/g)
+ * (a push of +F at history step s lowers the y velocity of sample s + 1 by dt·F/mass,
+ * zmp_controller.py:105-106; r_1 is exactly 0: a velocity kick moves neither c nor c̈ of the
+ * next sample).
+ *   hist, zmax, zmin, bounds_stride, lengths : as zmpc_walk_metrics (n_b clamped the same way)
+ *   push_steps    : NULL: the full map, force and limit are [B, n, 2];
+ *                   [B] int64: the single-step form, force and limit are [B, 2], the entries of
+ *                   step push_steps[b] of walk b (a step outside [0, n_b − 2) gives +inf and −1)
+ *   max_violation : t >= 0, the excursion beyond the support box that still passes
+ *   mass          : the robot's mass m in kg (the plan holds dt, h/g and the gains, not m)
+ *   force         : per walk b, with z0_i = c_i − (h/g)·c̈_i the y-axis ZMP of the history
+ *                   (uncontracted, as zmpc_walk_metrics), up_i = (zmax_i − z0_i) + t and
+ *                   dn_i = (z0_i − zmin_i) + t:
+ *       force[b, s, 0] (a +y push) = min over s < i < n_b of
+ *                      (r_d > 0 ? up_i / r_d : r_d < 0 ? dn_i / (−r_d) : +inf),  d = i − s
+ *       force[b, s, 1] (a −y push) = the same with up and dn swapped
+ *                   Entries with s >= n_b − 2, and entries that no sample constrains, are +inf.
+ *                   A walk that fails with no push — v_i = max(z − zmax, zmin − z, 0) > t on
+ *                   either axis at some i < n_b, zmpc_walk_metrics' test — or that holds a
+ *                   non-finite state value in a live sample of either axis is NaN in every entry.
+ *                   The map is not capped.  If the history already carries a push, the entries
+ *                   are the largest additional push.
+ *   limit         : int32, shaped as force, or NULL: the smallest i that attains the minimum
+ *                   (the sample that leaves its box first); −1 for +inf and NaN entries
+ *   response      : [n] or NULL: receives r_0 .. r_(n−1)
+ * No candidate is formed from r_d = 0 and no product 0·inf: a sample exactly on its bound with
+ * t = 0 gives 0.  The candidates are margin × (1/|r_d|), a few ulp from the quotient.  The
+ * minima run in an order fixed by the lane numbers: two calls on the same input agree bit for
+ * bit, and the single-step form returns the full map's rows bit for bit.  The response table is
+ * recomputed per call into a stream-ordered workspace of 2n doubles.
+ * The plan must be non-strict (it supplies kx, A, B, h/g and dt): a strict plan returns
+ * ZMPC_ESTATE — the response of a clamped controller is not affine, bisect over pushed rollouts
+ * there (ZMPController.critical_force).  The full map keeps a walk's margins in LDS: n > 10112
+ * returns ZMPC_ESTATE with the limit in the message; the single-step form takes any n.  Nothing
+ * is launched on a refusal.  ZMPC_EINVAL before any device call: NULL plan or (B > 0) NULL hist,
+ * zmax, zmin or force; B < 0; n < 1; max_violation < 0 or NaN; mass not finite and positive; a
+ * bad bounds_stride.  B = 0 does nothing.  Additive to ABI 7.
+ */
+int zmpc_push_map(const zmpc_plan* plan, int64_t B, int64_t n, const double* hist,
+                  const double* zmax, const double* zmin, int64_t bounds_stride,
+                  const int64_t* lengths, const int64_t* push_steps, double max_violation,
+                  double mass, double* force, int32_t* limit, double* response, void* stream);
+
+/*
  * Batched CoP-bound producer: CoPGenerator.generate_cop_trajectory
  * (generators/cop_generator.py:34-115) over the footstep plan of
  * generators/footstep_generator.py:19-49, one walk per set of parameters.

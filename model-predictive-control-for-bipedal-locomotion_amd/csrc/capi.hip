@@ -94,6 +94,7 @@ int zmpc_plan_create(int device, int32_t N, double T, double T2_2, double T3_6, 
     if ((e = zmpc_strict_set_attrs()) != hipSuccess) return hip_fail(e, "set LDS attrs");
     if ((e = zmpc_strict_lq_set_attrs()) != hipSuccess) return hip_fail(e, "set LDS attrs");
     if ((e = zmpc_herdt_set_attrs()) != hipSuccess) return hip_fail(e, "set LDS attrs");
+    if ((e = zmpc_push_map_set_attrs()) != hipSuccess) return hip_fail(e, "set LDS attrs");
     // the strict solvers' per-launch workspaces come from the stream-ordered pool: keep up to
     // ZMPC_POOL_KEEP_MB (default 4096) of freed blocks in the pool across synchronisations
     // instead of returning them to the driver every time; anything above is released
@@ -439,6 +440,38 @@ int zmpc_rollout_metrics(const zmpc_plan* P, int64_t B, int64_t n, const double*
   const hipError_t e =
       zmpc_launch_rollout_metrics(P, rc, lengths, metrics, (hipStream_t)stream);
   return launch_result(e, std::string(), "zmpc_rollout_metrics");
+}
+
+int zmpc_push_map(const zmpc_plan* P, int64_t B, int64_t n, const double* hist,
+                  const double* zmax, const double* zmin, int64_t bounds_stride,
+                  const int64_t* lengths, const int64_t* push_steps, double max_violation,
+                  double mass, double* force, int32_t* limit, double* response, void* stream) {
+  g_err.clear();
+  if (!P) return fail(ZMPC_EINVAL, "NULL plan");
+  if (B < 0 || n < 1) return fail(ZMPC_EINVAL, "need B >= 0 and n >= 1");
+  if (!(max_violation >= 0)) return fail(ZMPC_EINVAL, "need max_violation >= 0");
+  if (!(mass > 0) || !(mass < __builtin_inf()))
+    return fail(ZMPC_EINVAL, "need a finite mass > 0");
+  if (bounds_stride != 0 && bounds_stride < 2 * n)
+    return fail(ZMPC_EINVAL, "bounds_stride must be 0 (shared CoP) or >= 2n");
+  if (B > 0 && (!hist || !zmax || !zmin || !force))
+    return fail(ZMPC_EINVAL, "NULL array argument");
+  if (B > 0x7fffffff) return fail(ZMPC_EINVAL, "batch too large");
+  if (n > (1 << 24)) return fail(ZMPC_EINVAL, "walk too long");
+  // refused before any device call, nothing is launched
+  if (P->strict)
+    return fail(ZMPC_ESTATE, "zmpc_push_map: the ZMP response of a strict (clamped) controller "
+                             "is not affine in the push (bisect over pushed rollouts instead: "
+                             "ZMPController.critical_force)");
+  const PushMapChoice c = choose_push_map(n, push_steps != nullptr);
+  if (!c.ok) return fail(ZMPC_ESTATE, std::string("zmpc_push_map: ") + c.why);
+  if (B == 0) return ZMPC_OK;
+  DeviceGuard g(P->device);
+  if (g.err != hipSuccess) return hip_fail(g.err, "hipSetDevice");
+  const hipError_t e =
+      zmpc_launch_push_map(P, B, n, hist, zmax, zmin, bounds_stride, lengths, push_steps,
+                           max_violation, mass, force, limit, response, (hipStream_t)stream);
+  return launch_result(e, std::string(), "zmpc_push_map");
 }
 
 static int herdt_check(const zmpc_plan* P, const zmpc_herdt_params* prm, int64_t B) {

@@ -332,6 +332,38 @@ inline MetChoice choose_unc_metrics(int N, int64_t n, bool shared_cop, int opt_r
 }
 
 // ---------------------------------------------------------------------------------------------
+// Push-robustness map (zmpc_push_map; pushmap.hip)
+
+// The full map keeps a walk's (up, dn) margin pairs in LDS, 16 bytes per sample plus 64 pairs of
+// +inf behind them, one workgroup per walk.  Its dynamic-LDS ceiling is the wide kernel's 159 KiB
+// (hipFuncSetAttribute refuses the full 160), so the longest walk has 159·64 − 64 samples.
+constexpr size_t kPushMapLdsCap = (size_t)159 * 1024;
+constexpr int64_t kPushMapMaxN = (int64_t)(kPushMapLdsCap / 16) - 64;  // 10112
+
+// The geometry of a zmpc_push_map launch of n-sample walks:
+//   full map     `waves` waves per walk (one per pair of 64-step blocks, 16 at the most) and `lds`
+//                bytes of dynamic LDS; ok = false past kPushMapMaxN, `why` states the limit;
+//   single step  one wave per walk, no LDS, any n the history entries take.
+struct PushMapChoice {
+  bool ok;
+  int waves;
+  size_t lds;
+  const char* why;
+};
+
+inline PushMapChoice choose_push_map(int64_t n, bool single_step) {
+  if (single_step) return PushMapChoice{true, 1, 0, nullptr};
+  if (n > kPushMapMaxN)
+    return PushMapChoice{false, 0, 0,
+                         "the full map keeps a walk's margins in LDS: at most 10112 samples per "
+                         "walk (the single-step form, push_steps, has no such limit)"};
+  const int64_t nblk = (n + 63) / 64;
+  const int waves = (int)std::min<int64_t>(16, std::max<int64_t>(1, (nblk + 1) / 2));
+  return PushMapChoice{true, waves, (size_t)(n + 64) * 16, nullptr};
+}
+static_assert(kPushMapMaxN == 10112 && kPushMapMaxN >= 4096, "the message states the limit");
+
+// ---------------------------------------------------------------------------------------------
 // Strict box-QP (strict_dispatch.hip and its backends)
 
 // Horizons of the reduced-Cholesky kernels (strict.hip: eight 64-slot column blocks).

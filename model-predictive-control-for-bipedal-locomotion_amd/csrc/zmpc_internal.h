@@ -116,6 +116,18 @@ hipError_t zmpc_launch_walk_metrics(const zmpc_plan* p, int64_t B, int64_t n, co
                                     const double* zmax, const double* zmin, int64_t bstride,
                                     const int64_t* lengths, double* metrics, hipStream_t s);
 
+// push-robustness map of a state history (pushmap.hip): the shapes dispatch.h choose_push_map
+// takes (the caller refuses the others first) on a non-strict plan, whose kx, T, T²/2, T³/6 and
+// h/g it reads; t = max_violation; push_steps null: the full map, else the single-step form;
+// lengths, limit and response may be NULL.  hipErrorOutOfMemory: the response table's
+// stream-ordered workspace (2n doubles) could not be allocated
+hipError_t zmpc_launch_push_map(const zmpc_plan* p, int64_t B, int64_t n, const double* hist,
+                                const double* zmax, const double* zmin, int64_t bstride,
+                                const int64_t* lengths, const int64_t* push_steps, double t,
+                                double mass, double* force, int32_t* limit, double* response,
+                                hipStream_t s);
+hipError_t zmpc_push_map_set_attrs();
+
 // unconstrained rollout / step (rollout.hip)
 hipError_t zmpc_launch_rollout_unc(const zmpc_plan* p, const RolloutCall& c, hipStream_t s,
                                    std::string* why);

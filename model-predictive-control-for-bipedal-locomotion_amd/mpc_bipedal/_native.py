@@ -90,6 +90,10 @@ SIGNATURES = {
                                             _c_dbl_p, _c_dbl_p, ctypes.c_int64, _c_dbl_p, _c_dbl_p,
                                             ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p,
                                             _c_dbl_p, ctypes.c_void_p, ctypes.c_void_p]),
+    "zmpc_push_map": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, _c_dbl_p,
+                                     _c_dbl_p, _c_dbl_p, ctypes.c_int64, ctypes.c_void_p,
+                                     ctypes.c_void_p, ctypes.c_double, ctypes.c_double, _c_dbl_p,
+                                     ctypes.c_void_p, _c_dbl_p, ctypes.c_void_p]),
     "zmpc_cop_generate": (ctypes.c_int, [ctypes.c_int, ctypes.c_int64, _c_dbl_p, ctypes.c_int64,
                                          _c_dbl_p, _c_dbl_p, ctypes.c_void_p, ctypes.c_void_p,
                                          ctypes.c_void_p]),

@@ -13,8 +13,10 @@ The Herdt joint footstep QP (``method="herdt"``, :203-531) runs on the device as
 Additions (not in the reference): ``generate_com_trajectory_batch`` /
 ``generate_state_trajectory_batch`` / ``generate_com_trajectory_herdt_batch`` for many walks or
 disturbance scenarios at once, taking and returning torch device tensors; ``walk_metrics`` (did
-the ZMP stay inside the support box, per walk, reduced on the device) and ``critical_force``
-(the largest push each scenario survives, by bisection over batched rollouts).
+the ZMP stay inside the support box, per walk, reduced on the device), ``critical_force``
+(the largest push each scenario survives, by bisection over batched rollouts), and for the
+unconstrained controller ``push_map`` / ``critical_force_exact`` (that push in closed form, at
+every step and in both directions, from one unpushed rollout).
 """
 
 import warnings
@@ -23,7 +25,7 @@ from typing import Optional, Tuple
 import numpy as np
 import torch
 
-from ..analysis import NMETRICS, WalkMetrics
+from ..analysis import NMETRICS, PushMap, WalkMetrics
 from ..config import MPCConfig
 from ..models.lipm_model import lipm_matrices
 from ..solver import get_plan
@@ -425,6 +427,74 @@ class ZMPController:
             lo, hi = torch.where(ok, mid, lo), torch.where(ok, hi, mid)
         nan = torch.full_like(lo, float("nan"))
         return torch.where(never, nan, lo), torch.where(never, nan, hi)
+
+    def _unpushed(self, z_max, z_min, x_init, walk_lengths, extra=()):
+        """One unpushed rollout for the push map: (plan, hist, zmax, zmin, lengths, B, n)."""
+        plan = self._plan()
+        if plan.strict:
+            raise RuntimeError("the push map needs the unconstrained controller: the ZMP response "
+                               "of a strict (clamped) plan is not affine in the push — use "
+                               "critical_force")
+        dev = torch.device("cuda", plan.device)
+        f64 = dict(dtype=torch.float64, device=dev)
+        zmax_t = torch.as_tensor(z_max, **f64).contiguous()
+        zmin_t = torch.as_tensor(z_min, **f64).contiguous()
+        n = int(zmax_t.shape[-2])
+        sizes = [int(np.shape(a)[0]) for a in (*extra, walk_lengths)
+                 if a is not None and np.ndim(a) == 1]
+        if x_init is not None:
+            x0 = torch.as_tensor(x_init, **f64)
+            B = int(x0.shape[0])
+        else:
+            B = int(zmax_t.shape[0]) if zmax_t.dim() == 3 else (sizes[0] if sizes else 1)
+            x0 = torch.zeros((B, 2, 3), **f64)
+        if any(s != B for s in sizes):
+            raise ValueError(f"force_step, direction and walk_lengths must be scalars or [B] = [{B}]")
+        lengths = None
+        if walk_lengths is not None:
+            lengths = torch.as_tensor(walk_lengths, dtype=torch.int64, device=dev).reshape(B)
+        hist, _ = plan.rollout(zmax_t, zmin_t, x0)
+        return plan, hist, zmax_t, zmin_t, lengths, B, n
+
+    def push_map(self, z_max, z_min, x_init=None, walk_lengths=None,
+                 max_violation: float = 1e-9) -> PushMap:
+        """At which phase of the gait, and in which direction, is each walk weakest (addition;
+        zmpc_push_map): one unpushed rollout, then the exact critical push of every (walk, push
+        step, direction) in one launch — the F_ext sweep of run_compare_resistance.py:87-197 at
+        every step at once.  x_init [B,2,3] or None; z_max, z_min [B,n,2] or a shared [n,2];
+        walk_lengths [B] live samples of ragged walks.  Returns analysis.PushMap on the device:
+        force [B,n,2] in newtons ([..., 0] a +y push at that history step, [..., 1] a −y push,
+        as zmp_controller.py:105-106 applies it), +inf where no sample limits the push (steps
+        from n_b − 2 on), NaN for a walk that fails with no push; limit [B,n,2] the sample that
+        leaves its box first; weakest() the per-walk minimum.  Unconstrained plans only."""
+        plan, hist, zmax_t, zmin_t, lengths, _, _ = self._unpushed(z_max, z_min, x_init,
+                                                                   walk_lengths)
+        force, limit = plan.push_map(hist, zmax_t, zmin_t, lengths=lengths,
+                                     max_violation=max_violation, mass=self.config.m)
+        return PushMap(force, limit)
+
+    def critical_force_exact(self, z_max, z_min, x_init=None, force_step=None, direction=+1,
+                             max_violation: float = 1e-9, walk_lengths=None):
+        """critical_force's scenarios (same conventions and defaults: force_step defaults to
+        n//2, or n_b//2 with walk_lengths; direction[b]·F newtons on the y axis) answered in
+        closed form (addition; the single-step form of zmpc_push_map): one unpushed rollout and
+        one launch instead of 32 pushed rollouts, a number instead of a bracket.  Returns [B]
+        forces on the device: NaN where the walk fails with no push, +inf where no push at that
+        step ever fails (critical_force reports its search limit there).  Only the ZMP criterion
+        (max_violation); raises on a strict plan."""
+        plan, hist, zmax_t, zmin_t, lengths, B, n = self._unpushed(
+            z_max, z_min, x_init, walk_lengths, extra=(force_step, direction))
+        dev = hist.device
+        if force_step is None:
+            step = torch.full((B,), n // 2, dtype=torch.int64, device=dev) if lengths is None \
+                else lengths // 2
+        else:
+            step = torch.as_tensor(force_step, dtype=torch.int64, device=dev).expand(B)
+        force, _ = plan.push_map(hist, zmax_t, zmin_t, lengths=lengths,
+                                 push_steps=step.contiguous(), max_violation=max_violation,
+                                 mass=self.config.m)
+        sign = torch.as_tensor(direction, dtype=torch.float64, device=dev).expand(B)
+        return torch.where(sign >= 0, force[:, 0], force[:, 1])
 
     # ------------------------------------------------------------------ internals
     def _rollout_host(self, x_init, y_init, z_max, z_min, kick, kick_step) -> np.ndarray:

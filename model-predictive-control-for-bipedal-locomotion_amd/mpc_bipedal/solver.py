@@ -285,6 +285,67 @@ class Plan:
         _native.check(rc, "zmpc_walk_metrics")
         return out
 
+    # -- push-robustness map (zmpc_push_map) -----------------------------------------------
+    def push_map(self, hist, zmax, zmin, lengths=None, push_steps=None, max_violation=1e-9,
+                 out=None, want_response=False, *, mass):
+        """Exact critical push of every (walk, push step, direction) from an unpushed state
+        history (zmpc_push_map, include/zmpc.h) → (force, limit) device tensors, with
+        want_response=True (force, limit, response [n]).
+
+        hist, zmax, zmin, lengths: as walk_metrics.  push_steps None: the full map, force float64
+        and limit int32 [B, n, 2] ([..., 0] a +y push, [..., 1] a −y push at step s); push_steps
+        [B]: the single-step form, [B, 2] for that step of each walk.  mass: the robot's mass in
+        kg (the plan does not hold it).  out: a (force, limit) pair of contiguous tensors of
+        those shapes on the plan's device to write into.  Asynchronous on the current stream.
+        Non-strict plans only: a strict plan raises NativeError (ZMPC_ESTATE), as does a full map
+        of walks longer than the kernel's LDS holds (10112 samples)."""
+        dev = self._dev()
+        if not isinstance(hist, torch.Tensor) or hist.dim() != 4 or hist.shape[2:] != (2, 3) \
+                or hist.dtype != torch.float64 or hist.device != dev or not hist.is_contiguous():
+            raise ValueError("hist must be a contiguous float64 [B, n, 2, 3] tensor on the "
+                             "plan's device")
+        B, n = int(hist.shape[0]), int(hist.shape[1])
+        if n < 1:
+            raise ValueError("hist must hold at least one sample per walk")
+        zmax = self._as_dev(zmax)
+        if zmax.dim() == 2:
+            shape, bstride = (n, 2), 0
+        else:
+            shape, bstride = (B, n, 2), 2 * n
+        if tuple(zmax.shape) != shape:
+            raise ValueError(f"z_max must be [B, n, 2] = [{B}, {n}, 2] or [n, 2], got "
+                             f"{tuple(zmax.shape)}")
+        zmin = self._as_dev(zmin, shape)
+        len_t = steps_t = None
+        if lengths is not None:
+            len_t = torch.as_tensor(lengths, dtype=torch.int64, device=dev).contiguous()
+            if tuple(len_t.shape) != (B,):
+                raise ValueError(f"lengths must be [B] = [{B}], got {tuple(len_t.shape)}")
+        if push_steps is not None:
+            steps_t = torch.as_tensor(push_steps, dtype=torch.int64, device=dev).contiguous()
+            if tuple(steps_t.shape) != (B,):
+                raise ValueError(f"push_steps must be [B] = [{B}], got {tuple(steps_t.shape)}")
+        oshape = (B, n, 2) if steps_t is None else (B, 2)
+        if out is None:
+            force = torch.empty(oshape, dtype=torch.float64, device=dev)
+            limit = torch.empty(oshape, dtype=torch.int32, device=dev)
+        else:
+            force, limit = out
+            for t, dt in ((force, torch.float64), (limit, torch.int32)):
+                if tuple(t.shape) != oshape or t.dtype != dt or t.device != dev or \
+                        not t.is_contiguous():
+                    raise ValueError(f"out must be (float64, int32) contiguous {oshape} tensors "
+                                     "on the plan's device")
+        resp = torch.empty(n, dtype=torch.float64, device=dev) if want_response else None
+        with torch.cuda.device(self.device):
+            stream = torch.cuda.current_stream(self.device).cuda_stream
+            rc = _native.load().zmpc_push_map(self._live(), B, n, _ptr(hist), _ptr(zmax),
+                                              _ptr(zmin), bstride, _ptr(len_t), _ptr(steps_t),
+                                              float(max_violation), float(mass), _ptr(force),
+                                              _ptr(limit), _ptr(resp), ctypes.c_void_p(stream))
+        _native.check(rc, "zmpc_push_map")
+        return (force, limit, resp) if want_response else (force, limit)
+
     # -- fused rollout-to-metrics (zmpc_rollout_metrics) -----------------------------------
     def _rollout_metrics_args(self, zmax, zmin, x0, kick, kick_step, lengths, out, status):
         dev = self._dev()
