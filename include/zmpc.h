@@ -321,6 +321,56 @@ int zmpc_push_map(const zmpc_plan* plan, int64_t B, int64_t n, const double* his
                   double mass, double* force, int32_t* limit, double* response, void* stream);
 
 /*
+ * Push-robustness map of sustained and shaped pushes, on either axis or both.  Everything is as
+ * in zmpc_push_map unless said here: the nominal test, the clamping of n_b, max_violation, NaN
+ * for a walk that fails unpushed, no cap, ties to the lower sample.  The same linear,
+ * time-invariant argument, with no new approximation:
+ *   - a push with force profile F·w_j during history steps s + j, j < duration = D, is a sum of
+ *     one-sample pushes, so it moves the ZMP of sample s + d by F·R_d with
+ *         R_d = Σ_{j = 0}^{min(D−1, d)} w_j·r_(d−j),  0 <= d < n,
+ *     summed in ascending j, uncontracted (r_d as zmpc_push_map; R_0 = R_1 = 0 always);
+ *   - the x axis runs the same closed loop with the same r: a push of +F on axis a lowers that
+ *     axis' velocity of sample s + j + 1 by dt·F·w_j/mass (the reference's convention for y,
+ *     mirrored for x);
+ *   - the axes decouple, so the critical magnitude along any planar direction follows from the
+ *     four columns +x, −x, +y, −y (analysis.PushMap.rose).
+ *   profile  : [duration] device doubles w_0 .. w_(D−1), or NULL: all ones, and the product is
+ *              skipped, so D = 1 gives R_d = r_d bit for bit.  Weights at j >= n are never read.
+ *              A push that runs past n_b − 1 is truncated by itself.  A non-finite weight gives
+ *              unspecified values in the entries it reaches; it never causes an out-of-range
+ *              access and no 0·inf is formed (terms with r = 0 are skipped).
+ *   duration : D >= 1, in samples
+ *   axes     : ZMPC_PUSH_AXIS_X: columns (+x, −x); ZMPC_PUSH_AXIS_Y: (+y, −y); both: (+x, −x,
+ *              +y, −y).  C = 2 or 4 columns.
+ *   force    : [B, n, C], or [B, C] with push_steps (the step rule of zmpc_push_map).  Per axis a,
+ *              with z0 that axis' uncontracted ZMP, up_i = (zmax_i − z0_i) + t and
+ *              dn_i = (z0_i − zmin_i) + t:
+ *       force[b, s, (+a)] = min over s < i < n_b of
+ *                      (R_d > 0 ? up_i / R_d : R_d < 0 ? dn_i / (−R_d) : +inf),  d = i − s
+ *       force[b, s, (−a)] = the same with up and dn swapped
+ *   limit    : int32, shaped as force, or NULL: the smallest i that attains the minimum
+ *   response : [n] or NULL: receives R_0 .. R_(n−1)
+ * With axes = ZMPC_PUSH_AXIS_Y, D = 1 and a NULL profile, force, limit and response are
+ * zmpc_push_map's bit for bit; a two-axis call equals the two one-axis calls column for column;
+ * the single-step form returns the full map's rows bit for bit; two calls on the same input
+ * agree bit for bit.  The shaped table is computed per call by a grid over the delays (n·min(D,
+ * n)/2 products) into a stream-ordered workspace of 5n doubles.  In the full map the axes take
+ * turns over the same LDS: n > 10112 returns ZMPC_ESTATE for one axis or two, with the limit in
+ * the message; the single-step form takes any n.  A strict plan returns ZMPC_ESTATE.  Nothing
+ * is launched on a refusal.  ZMPC_EINVAL before any device call: zmpc_push_map's cases,
+ * duration < 1, axes outside 1..3.  B = 0 does nothing.  Additive to ABI 7.
+ */
+#define ZMPC_PUSH_AXIS_X 1
+#define ZMPC_PUSH_AXIS_Y 2
+int zmpc_push_map_shaped(const zmpc_plan* plan, int64_t B, int64_t n, const double* hist,
+                         const double* zmax, const double* zmin, int64_t bounds_stride,
+                         const int64_t* lengths, const int64_t* push_steps,
+                         const double* profile /* [duration] device, or NULL */,
+                         int64_t duration, int32_t axes, double max_violation, double mass,
+                         double* force, int32_t* limit, double* response /* [n] R_d or NULL */,
+                         void* stream);
+
+/*
  * Batched CoP-bound producer: CoPGenerator.generate_cop_trajectory
  * (generators/cop_generator.py:34-115) over the footstep plan of
  * generators/footstep_generator.py:19-49, one walk per set of parameters.

@@ -474,6 +474,42 @@ int zmpc_push_map(const zmpc_plan* P, int64_t B, int64_t n, const double* hist,
   return launch_result(e, std::string(), "zmpc_push_map");
 }
 
+int zmpc_push_map_shaped(const zmpc_plan* P, int64_t B, int64_t n, const double* hist,
+                         const double* zmax, const double* zmin, int64_t bounds_stride,
+                         const int64_t* lengths, const int64_t* push_steps, const double* profile,
+                         int64_t duration, int32_t axes, double max_violation, double mass,
+                         double* force, int32_t* limit, double* response, void* stream) {
+  g_err.clear();
+  if (!P) return fail(ZMPC_EINVAL, "NULL plan");
+  if (B < 0 || n < 1) return fail(ZMPC_EINVAL, "need B >= 0 and n >= 1");
+  if (!(max_violation >= 0)) return fail(ZMPC_EINVAL, "need max_violation >= 0");
+  if (!(mass > 0) || !(mass < __builtin_inf()))
+    return fail(ZMPC_EINVAL, "need a finite mass > 0");
+  if (bounds_stride != 0 && bounds_stride < 2 * n)
+    return fail(ZMPC_EINVAL, "bounds_stride must be 0 (shared CoP) or >= 2n");
+  if (duration < 1) return fail(ZMPC_EINVAL, "need duration >= 1 (samples)");
+  if (axes < 1 || axes > (ZMPC_PUSH_AXIS_X | ZMPC_PUSH_AXIS_Y))
+    return fail(ZMPC_EINVAL, "axes must be 1 (the x axis), 2 (the y axis) or 3 (both)");
+  if (B > 0 && (!hist || !zmax || !zmin || !force))
+    return fail(ZMPC_EINVAL, "NULL array argument");
+  if (B > 0x7fffffff) return fail(ZMPC_EINVAL, "batch too large");
+  if (n > (1 << 24)) return fail(ZMPC_EINVAL, "walk too long");
+  // refused before any device call, nothing is launched
+  if (P->strict)
+    return fail(ZMPC_ESTATE, "zmpc_push_map_shaped: the ZMP response of a strict (clamped) "
+                             "controller is not affine in the push (bisect over pushed rollouts "
+                             "instead: ZMPController.critical_force)");
+  const PushMapChoice c = choose_push_shaped(n, push_steps != nullptr, axes == 3 ? 2 : 1);
+  if (!c.ok) return fail(ZMPC_ESTATE, std::string("zmpc_push_map_shaped: ") + c.why);
+  if (B == 0) return ZMPC_OK;
+  DeviceGuard g(P->device);
+  if (g.err != hipSuccess) return hip_fail(g.err, "hipSetDevice");
+  const hipError_t e = zmpc_launch_push_map_shaped(
+      P, B, n, hist, zmax, zmin, bounds_stride, lengths, push_steps, profile, duration, axes,
+      max_violation, mass, force, limit, response, (hipStream_t)stream);
+  return launch_result(e, std::string(), "zmpc_push_map_shaped");
+}
+
 static int herdt_check(const zmpc_plan* P, const zmpc_herdt_params* prm, int64_t B) {
   if (!P || !prm) return fail(ZMPC_EINVAL, "NULL plan or params");
   if (B < 0) return fail(ZMPC_EINVAL, "B < 0");

@@ -363,6 +363,22 @@ inline PushMapChoice choose_push_map(int64_t n, bool single_step) {
 }
 static_assert(kPushMapMaxN == 10112 && kPushMapMaxN >= 4096, "the message states the limit");
 
+// The geometry of a zmpc_push_map_shaped launch over naxes = 1 or 2 axes.  Two axes take turns
+// over the same 16 bytes per sample (the second fill re-reads the walk's 48·n bytes from cache:
+// n samples against the n²/2 pairs of the map loop), so the LDS, the waves and the longest walk
+// are choose_push_map's for either count.  Both axes' margins in LDS at once (32 bytes per
+// sample) would halve the longest walk to 5024 samples and double the loop's LDS bytes and live
+// accumulators to save the second, cached pass and half the scalar table loads.
+inline PushMapChoice choose_push_shaped(int64_t n, bool single_step, int naxes) {
+  if (naxes != 1 && naxes != 2) return PushMapChoice{false, 0, 0, "one or two axes"};
+  PushMapChoice c = choose_push_map(n, single_step);
+  if (!c.ok)
+    c.why = "the full map keeps a walk's margins in LDS, one axis at a time: at most 10112 "
+            "samples per walk for one axis or two (the single-step form, push_steps, has no "
+            "such limit)";
+  return c;
+}
+
 // ---------------------------------------------------------------------------------------------
 // Strict box-QP (strict_dispatch.hip and its backends)
 

@@ -29,19 +29,16 @@
 // Guards: a candidate is never formed from r_d = 0; where q_d is not a positive normal number
 // (|r_d| denormal or non-finite) the candidate is the division x/|r_d| itself, so no 0·inf is
 // formed and a sample exactly on its bound with t = 0 gives F = 0.
+//
+// zmpc_push_map_shaped (pushshaped.hip) shapes the table for pushes that last several samples and
+// adds the x axis; its y-only launches run the map and step kernels here on the shaped table
+// (zmpc_push_base_table, zmpc_push_map_on_table below).
+#include "push_common.h"
 #include "zmpc_internal.h"
 
 namespace {
 
 #pragma clang fp contract(off)
-
-struct pair_t {
-  double x, y;
-};
-
-struct ipair_t {
-  int32_t x, y;
-};
 
 // ---------------------------------------------------------------------------------------------
 // Response table: tab[d] = (r_d, q_d = 1/|r_d|) (q_d = 0 where r_d = 0), one 16-byte scalar load
@@ -104,12 +101,6 @@ zmpc_push_response_kernel(int64_t n, const double* __restrict__ kx, double T, do
 }
 
 // ---------------------------------------------------------------------------------------------
-// The candidate of one margin x >= 0 under a response of magnitude ra with reciprocal q; `fast`:
-// q is a positive normal number
-__device__ __forceinline__ double push_cand(double x, double q, double ra, bool fast) {
-  return fast ? x * q : x / ra;
-}
-
 // One sample of a walk: its y-axis margins, and whether it fails the nominal test (a non-finite
 // state value, or a violation above t on either axis — the test of metrics.hip AxisAcc::add)
 struct Sample {
@@ -134,24 +125,6 @@ __device__ __forceinline__ Sample push_sample(const pair_t* __restrict__ h,
   s.up = (u.y - zy) + t;
   s.dn = (zy - l.y) + t;
   return s;
-}
-
-// One (sample, step) pair in both directions: mi = (up_i, dn_i) of sample i.  POS: r_d > 0 (a +y push raises the ZMP: up limits
-// +, dn limits −).  Strict <: of equal candidates the first one met stays.
-template <bool POS>
-__device__ __forceinline__ void push_pair(const pair_t mi, int i, double q, double ra,
-                                          const bool fast, double& f0, double& f1, int& i0,
-                                          int& i1) {
-  const double c0 = push_cand(POS ? mi.x : mi.y, q, ra, fast);
-  const double c1 = push_cand(POS ? mi.y : mi.x, q, ra, fast);
-  if (c0 < f0) {
-    f0 = c0;
-    i0 = i;
-  }
-  if (c1 < f1) {
-    f1 = c1;
-    i1 = i;
-  }
 }
 
 __global__ void __launch_bounds__(1024)
@@ -238,9 +211,7 @@ zmpc_push_map_kernel(int64_t n, const double* __restrict__ hist, const double* _
 }
 
 // ---------------------------------------------------------------------------------------------
-// Single-step form: one wave per walk, four walks per workgroup, lanes over samples.
-constexpr int kStepWaves = 4;
-
+// Single-step form: one wave per walk, four walks per workgroup (kStepWaves), lanes over samples.
 __global__ void __launch_bounds__(64 * kStepWaves)
 zmpc_push_step_kernel(int64_t B, int64_t n, const double* __restrict__ hist,
                       const double* __restrict__ zmax, const double* __restrict__ zmin,
@@ -307,8 +278,32 @@ zmpc_push_step_kernel(int64_t B, int64_t n, const double* __restrict__ hist,
 }  // namespace
 
 hipError_t zmpc_push_map_set_attrs() {
-  return hipFuncSetAttribute((const void*)zmpc_push_map_kernel,
-                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)kPushMapLdsCap);
+  const hipError_t e =
+      hipFuncSetAttribute((const void*)zmpc_push_map_kernel,
+                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)kPushMapLdsCap);
+  return e != hipSuccess ? e : zmpc_push_shaped_set_attrs();
+}
+
+void zmpc_push_base_table(const zmpc_plan* p, int64_t n, double mass, void* tab, double* response,
+                          hipStream_t s) {
+  hipLaunchKernelGGL(zmpc_push_response_kernel, dim3(1), dim3(64), 0, s, n, p->kx, p->T, p->T2_2,
+                     p->T3_6, p->hg, p->T / mass, static_cast<pair_t*>(tab), response);
+}
+
+void zmpc_push_map_on_table(const zmpc_plan* p, int64_t B, int64_t n, const double* hist,
+                            const double* zmax, const double* zmin, int64_t bstride,
+                            const int64_t* lengths, const int64_t* push_steps, double t,
+                            const void* table, double* force, int32_t* limit, hipStream_t s) {
+  const PushMapChoice c = choose_push_map(n, push_steps != nullptr);
+  const pair_t* tab = static_cast<const pair_t*>(table);
+  if (push_steps) {
+    const unsigned grid = (unsigned)((B + kStepWaves - 1) / kStepWaves);
+    hipLaunchKernelGGL(zmpc_push_step_kernel, dim3(grid), dim3(64 * kStepWaves), 0, s, B, n, hist,
+                       zmax, zmin, bstride, lengths, push_steps, p->hg, t, tab, force, limit);
+  } else {
+    hipLaunchKernelGGL(zmpc_push_map_kernel, dim3((unsigned)B), dim3(64 * c.waves), c.lds, s, n,
+                       hist, zmax, zmin, bstride, lengths, p->hg, t, tab, force, limit);
+  }
 }
 
 hipError_t zmpc_launch_push_map(const zmpc_plan* p, int64_t B, int64_t n, const double* hist,
@@ -316,25 +311,15 @@ hipError_t zmpc_launch_push_map(const zmpc_plan* p, int64_t B, int64_t n, const 
                                 const int64_t* lengths, const int64_t* push_steps, double t,
                                 double mass, double* force, int32_t* limit, double* response,
                                 hipStream_t s) {
-  const PushMapChoice c = choose_push_map(n, push_steps != nullptr);
   // the response table of this n, recomputed per launch into a stream-ordered workspace (a plan
   // is shared by threads and streams, each with an n of its own)
   pair_t* tab = nullptr;
   hipError_t e = hipMallocAsync((void**)&tab, (size_t)n * sizeof(pair_t), s);
   if (e != hipSuccess) return hipErrorOutOfMemory;
-  hipLaunchKernelGGL(zmpc_push_response_kernel, dim3(1), dim3(64), 0, s, n, p->kx, p->T, p->T2_2,
-                     p->T3_6, p->hg, p->T / mass, tab, response);
-  if (B > 0) {
-    if (push_steps) {
-      const unsigned grid = (unsigned)((B + kStepWaves - 1) / kStepWaves);
-      hipLaunchKernelGGL(zmpc_push_step_kernel, dim3(grid), dim3(64 * kStepWaves), 0, s, B, n,
-                         hist, zmax, zmin, bstride, lengths, push_steps, p->hg, t, tab, force,
-                         limit);
-    } else {
-      hipLaunchKernelGGL(zmpc_push_map_kernel, dim3((unsigned)B), dim3(64 * c.waves), c.lds, s, n,
-                         hist, zmax, zmin, bstride, lengths, p->hg, t, tab, force, limit);
-    }
-  }
+  zmpc_push_base_table(p, n, mass, tab, response, s);
+  if (B > 0)
+    zmpc_push_map_on_table(p, B, n, hist, zmax, zmin, bstride, lengths, push_steps, t, tab, force,
+                           limit, s);
   e = hipGetLastError();
   const hipError_t ef = hipFreeAsync(tab, s);
   return e != hipSuccess ? e : ef;

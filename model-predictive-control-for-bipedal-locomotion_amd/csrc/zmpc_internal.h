@@ -126,6 +126,27 @@ hipError_t zmpc_launch_push_map(const zmpc_plan* p, int64_t B, int64_t n, const 
                                 const int64_t* lengths, const int64_t* push_steps, double t,
                                 double mass, double* force, int32_t* limit, double* response,
                                 hipStream_t s);
+// the two halves of zmpc_launch_push_map, for pushshaped.hip: the one-sample response of this n
+// into tab ([n] 16-byte pairs (r_d, 1/|r_d|)) and response ([n] doubles, may be NULL); and the map
+// or single-step kernels of zmpc_push_map on a table of that layout (B > 0)
+void zmpc_push_base_table(const zmpc_plan* p, int64_t n, double mass, void* tab, double* response,
+                          hipStream_t s);
+void zmpc_push_map_on_table(const zmpc_plan* p, int64_t B, int64_t n, const double* hist,
+                            const double* zmax, const double* zmin, int64_t bstride,
+                            const int64_t* lengths, const int64_t* push_steps, double t,
+                            const void* table, double* force, int32_t* limit, hipStream_t s);
+hipError_t zmpc_push_shaped_set_attrs();
+
+// the shaped and two-axis form (zmpc_push_map_shaped, pushshaped.hip): the shapes choose_push_shaped takes;
+// profile (device, [duration]) may be NULL; axes = ZMPC_PUSH_AXIS_X, _Y or both; force and limit
+// hold 2 columns per step and axis.  Workspace: 5n doubles
+hipError_t zmpc_launch_push_map_shaped(const zmpc_plan* p, int64_t B, int64_t n,
+                                       const double* hist, const double* zmax,
+                                       const double* zmin, int64_t bstride,
+                                       const int64_t* lengths, const int64_t* push_steps,
+                                       const double* profile, int64_t duration, int axes, double t,
+                                       double mass, double* force, int32_t* limit,
+                                       double* response, hipStream_t s);
 hipError_t zmpc_push_map_set_attrs();
 
 // unconstrained rollout / step (rollout.hip)

@@ -94,6 +94,13 @@ SIGNATURES = {
                                      _c_dbl_p, _c_dbl_p, ctypes.c_int64, ctypes.c_void_p,
                                      ctypes.c_void_p, ctypes.c_double, ctypes.c_double, _c_dbl_p,
                                      ctypes.c_void_p, _c_dbl_p, ctypes.c_void_p]),
+    # ... push_steps, profile, duration, axes, max_violation, mass, force, limit, response, stream
+    "zmpc_push_map_shaped": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64,
+                                            _c_dbl_p, _c_dbl_p, _c_dbl_p, ctypes.c_int64,
+                                            ctypes.c_void_p, ctypes.c_void_p, _c_dbl_p,
+                                            ctypes.c_int64, ctypes.c_int32, ctypes.c_double,
+                                            ctypes.c_double, _c_dbl_p, ctypes.c_void_p, _c_dbl_p,
+                                            ctypes.c_void_p]),
     "zmpc_cop_generate": (ctypes.c_int, [ctypes.c_int, ctypes.c_int64, _c_dbl_p, ctypes.c_int64,
                                          _c_dbl_p, _c_dbl_p, ctypes.c_void_p, ctypes.c_void_p,
                                          ctypes.c_void_p]),

@@ -13,6 +13,12 @@ only on the delay between push and sample (``push_response``), and ``zmpc_push_m
 (``csrc/pushmap.hip``) evaluates it for every push step and both directions of an unpushed
 history.  ``push_map_reference`` is that map in NumPy (again the checker, never a fallback) and
 ``PushMap`` names its outputs.
+
+A push that lasts several samples, with or without a force profile, has the response
+``shaped_response``; the x axis runs the same closed loop, and the axes decouple.
+``zmpc_push_map_shaped`` (``csrc/pushshaped.hip``) evaluates that on either axis or both,
+``push_map_shaped_reference`` is its checker, and ``PushMap.weakest_push`` and ``PushMap.rose``
+(``planar_push``) read the columns (+x, −x, +y, −y), the latter along any planar direction.
 """
 
 import numpy as np
@@ -168,30 +174,244 @@ def push_map_reference(hist, zmax, zmin, r, hg, lengths=None, max_violation=0.0,
     return f1, l1
 
 
+AXES = {"x": 1, "y": 2, "xy": 3}  # include/zmpc.h ZMPC_PUSH_AXIS_X | ZMPC_PUSH_AXIS_Y
+
+
+def check_profile(duration, profile):
+    """The (duration, profile) pair of a shaped push as (D, w): D >= 1 an int, w None (all ones)
+    or a finite float64 [D] array.  Raises ValueError otherwise."""
+    if isinstance(duration, bool) or not isinstance(duration, (int, np.integer)) or duration < 1:
+        raise ValueError(f"duration must be an integer >= 1 (samples), got {duration!r}")
+    if profile is None:
+        return int(duration), None
+    w = np.asarray(profile, np.float64)
+    if w.ndim != 1 or w.shape[0] != duration:
+        raise ValueError(f"profile must hold duration = {duration} weights, got shape "
+                         f"{tuple(w.shape)}")
+    if not np.isfinite(w).all():
+        raise ValueError("profile must be finite")
+    return int(duration), w
+
+
+def shaped_response(r, duration, profile=None):
+    """Response by delay of a push that lasts `duration` samples with force profile F·w_j during
+    history steps s + j → R [n], R_d = Σ_{j=0}^{min(D−1, d)} w_j·r_{d−j}, summed in ascending j.
+
+    r [n] is the one-sample response (push_response, or the device's table); profile None: all
+    ones, and the product is skipped, so duration 1 returns r bit for bit.  Weights at j >= n are
+    never read.  R_0 = R_1 = 0 as r_0 = r_1 = 0."""
+    D, w = check_profile(duration, profile)
+    r = np.asarray(r, np.float64)
+    n = r.shape[0]
+    R = np.zeros(n)
+    for j in range(min(D, n)):
+        R[j:] += r[:n - j] if w is None else w[j] * r[:n - j]
+    return R
+
+
+def _axis_columns(up, dn, R, nb, force, limit, gap=None):
+    """force[s, 0:2], limit[s, 0:2] (and gap[s, 0:2], the relative distance of the runner-up
+    candidate) of one axis of one walk from its margins up, dn [nb] and the response R."""
+    aR = np.abs(R)
+    for st in range(nb - 2):
+        rd, ad = R[1:nb - st], aR[1:nb - st]                             # delays of i = st+1 …
+        pos, neg = rd > 0, rd < 0
+        with np.errstate(over="ignore", divide="ignore", invalid="ignore"):
+            cu, cd = up[st + 1:nb] / ad, dn[st + 1:nb] / ad               # (masked where r = 0)
+        for k, (a, c) in enumerate(((cu, cd), (cd, cu))):                 # +: up limits r > 0
+            f = np.where(pos, a, np.where(neg, c, np.inf))
+            j = int(np.argmin(f))                                        # the first minimum
+            if f[j] < np.inf:
+                force[st, k] = f[j]
+                limit[st, k] = st + 1 + j
+                if gap is not None:
+                    two = np.partition(f, 1)[:2] if len(f) > 1 else f
+                    if len(two) < 2 or two[1] == np.inf:
+                        gap[st, k] = np.inf
+                    elif two[0] == 0:
+                        gap[st, k] = np.inf if two[1] > 0 else 0.0
+                    else:
+                        gap[st, k] = (two[1] - two[0]) / two[0]
+
+
+def push_map_shaped_reference(hist, zmax, zmin, r, hg, lengths=None, max_violation=0.0,
+                              push_steps=None, duration=1, profile=None, axes="y",
+                              return_gap=False):
+    """The statement of include/zmpc.h zmpc_push_map_shaped in NumPy, with division: the checker
+    of the kernels, never a fallback → (force, limit).
+
+    Arguments as push_map_reference; r [n] is the one-sample response, shaped here by
+    shaped_response(r, duration, profile) (hand in an already shaped table with duration = 1).
+    axes "x", "y" or "xy": the columns are (+x, −x), (+y, −y) or (+x, −x, +y, −y), C of them;
+    force float64 and limit int32 are [B, n, C], or [B, C] with push_steps.  return_gap: also the
+    relative gap between each finite entry's minimum and its runner-up candidate (inf where one
+    sample alone constrains the push, NaN elsewhere), shaped as force: an index comparison is
+    fair where it exceeds the rounding of the candidates."""
+    if axes not in AXES:
+        raise ValueError(f"axes must be 'x', 'y' or 'xy', got {axes!r}")
+    hist = np.asarray(hist, np.float64)
+    zmax = np.asarray(zmax, np.float64)
+    zmin = np.asarray(zmin, np.float64)
+    B, n = hist.shape[:2]
+    R = shaped_response(np.asarray(r, np.float64)[:n], duration, profile)
+    t = float(max_violation)
+    cols = [a for a in (0, 1) if AXES[axes] >> a & 1]
+    C = 2 * len(cols)
+    force = np.full((B, n, C), np.inf)
+    limit = np.full((B, n, C), -1, np.int32)
+    gap = np.full((B, n, C), np.nan) if return_gap else None
+    for b in range(B):
+        nb = n if lengths is None else min(max(int(lengths[b]), 1), n)
+        hi = (zmax if zmax.ndim == 2 else zmax[b])[:nb]
+        lo = (zmin if zmin.ndim == 2 else zmin[b])[:nb]
+        s = hist[b, :nb]
+        z = s[:, :, 0] - hg * s[:, :, 2]                                 # [nb, 2]
+        v = np.fmax(np.fmax(z - hi, lo - z), 0.0)
+        if not np.isfinite(s).all() or (v > t).any():
+            force[b] = np.nan
+            continue
+        for c, a in enumerate(cols):
+            up = (hi[:, a] - z[:, a]) + t
+            dn = (z[:, a] - lo[:, a]) + t
+            _axis_columns(up, dn, R, nb, force[b, :, 2 * c:2 * c + 2],
+                          limit[b, :, 2 * c:2 * c + 2],
+                          None if gap is None else gap[b, :, 2 * c:2 * c + 2])
+    if push_steps is not None:
+        f1 = np.full((B, C), np.inf)
+        l1 = np.full((B, C), -1, np.int32)
+        g1 = np.full((B, C), np.nan)
+        for b in range(B):
+            nb = n if lengths is None else min(max(int(lengths[b]), 1), n)
+            st = int(push_steps[b])
+            if 0 <= st < nb - 2:
+                f1[b], l1[b] = force[b, st], limit[b, st]
+                if gap is not None:
+                    g1[b] = gap[b, st]
+            elif np.isnan(force[b, 0, 0]):
+                f1[b] = np.nan
+        force, limit, gap = f1, l1, (g1 if return_gap else None)
+    return (force, limit, gap) if return_gap else (force, limit)
+
+
+def planar_push(force, limit, direction):
+    """Critical magnitude of a push along a planar direction from the four columns of an "xy"
+    map → (magnitude, limiting sample).  force, limit [..., 4] (+x, −x, +y, −y), tensors or
+    arrays; direction [..., 2] unit vectors (dx, dy), a NumPy array that broadcasts against the
+    leading dimensions.  The axes decouple, so the push F·(dx, dy) survives while F·|dx| <=
+    F_x(sign dx) and F·|dy| <= F_y(sign dy): the magnitude is min(F_x/|dx|, F_y/|dy|), an
+    exactly-zero component gives no limit from its axis, NaN stays NaN."""
+    d = np.asarray(direction, np.float64)
+    cx = (d[..., 0] < 0).astype(np.int64)
+    cy = 2 + (d[..., 1] < 0)
+    ax, ay = np.abs(d[..., 0]), np.abs(d[..., 1])
+    if hasattr(force, "detach"):  # torch
+        import torch
+        dev = force.device
+        ax, ay = (torch.as_tensor(a, dtype=force.dtype, device=dev) for a in (ax, ay))
+        shape = torch.broadcast_shapes(force.shape[:-1], ax.shape)
+        cx, cy = (torch.as_tensor(np.asarray(c), device=dev).expand(shape).unsqueeze(-1)
+                  for c in (cx, cy))
+        fe, le = force.expand(*shape, 4), limit.expand(*shape, 4)
+        fx, fy = fe.gather(-1, cx).squeeze(-1), fe.gather(-1, cy).squeeze(-1)
+        lx, ly = le.gather(-1, cx).squeeze(-1), le.gather(-1, cy).squeeze(-1)
+        inf = torch.full_like(fx, float("inf"))
+        mx = torch.where(ax > 0, fx / ax, inf)
+        my = torch.where(ay > 0, fy / ay, inf)
+        return torch.minimum(mx, my), torch.where(mx <= my, lx, ly)
+    shape = np.broadcast_shapes(force.shape[:-1], ax.shape)
+    cx, cy = (np.broadcast_to(c, shape)[..., None] for c in (cx, cy))
+    fe, le = np.broadcast_to(force, shape + (4,)), np.broadcast_to(limit, shape + (4,))
+    fx, fy = (np.take_along_axis(fe, c, -1)[..., 0] for c in (cx, cy))
+    lx, ly = (np.take_along_axis(le, c, -1)[..., 0] for c in (cx, cy))
+    with np.errstate(divide="ignore", invalid="ignore"):
+        mx = np.where(ax > 0, fx / ax, np.inf)
+        my = np.where(ay > 0, fy / ay, np.inf)
+    return np.minimum(mx, my), np.where(mx <= my, lx, ly)
+
+
+def unit_directions(directions):
+    """[K, 2] (or [..., 2]) finite non-zero planar vectors, normalised → float64 array."""
+    d = np.asarray(directions, np.float64)
+    if d.ndim < 1 or d.shape[-1] != 2 or not np.isfinite(d).all():
+        raise ValueError(f"directions must be finite [..., 2] vectors, got shape {tuple(d.shape)}")
+    norm = np.hypot(d[..., 0], d[..., 1])
+    if (norm == 0).any():
+        raise ValueError("a direction must not be the zero vector")
+    return d / norm[..., None]
+
+
 class PushMap:
-    """The push-robustness map of a batch of walks: ``force`` [B, n, 2] (N; [..., 0] a +y push,
-    [..., 1] a −y push, at history step s) and ``limit`` [B, n, 2] (int32, the sample that leaves
-    its box first, −1 where no sample does or the walk fails unpushed), tensors or arrays; views,
-    no copies.  ``response`` [n] is the ZMP response by delay when it was asked for."""
+    """The push-robustness map of a batch of walks: ``force`` [B, n, C] (N, at history step s) and
+    ``limit`` [B, n, C] (int32, the sample that leaves its box first, −1 where no sample does or
+    the walk fails unpushed), tensors or arrays; views, no copies.  ``axes`` names the columns:
+    "y" (the default) [..., 0] a +y push and [..., 1] a −y push, "x" the same on the x axis, "xy"
+    (+x, −x, +y, −y).  ``response`` [n] is the ZMP response by delay when it was asked for."""
 
-    __slots__ = ("force", "limit", "response")
+    __slots__ = ("force", "limit", "response", "axes")
 
-    def __init__(self, force, limit, response=None):
-        if force.ndim != 3 or force.shape[2] != 2 or tuple(limit.shape) != tuple(force.shape):
-            raise ValueError(f"force and limit must both be [B, n, 2], got {tuple(force.shape)} "
+    def __init__(self, force, limit, response=None, axes="y"):
+        if axes not in AXES:
+            raise ValueError(f"axes must be 'x', 'y' or 'xy', got {axes!r}")
+        C = 4 if axes == "xy" else 2
+        if force.ndim != 3 or force.shape[2] != C or tuple(limit.shape) != tuple(force.shape):
+            raise ValueError(f"force and limit must both be [B, n, {C}], got {tuple(force.shape)} "
                              f"and {tuple(limit.shape)}")
-        self.force, self.limit, self.response = force, limit, response
+        self.force, self.limit, self.response, self.axes = force, limit, response, axes
 
     def __len__(self):
         return int(self.force.shape[0])
 
     def __repr__(self):
-        return f"PushMap(B={len(self)}, n={int(self.force.shape[1])})"
+        tail = "" if self.axes == "y" else f", axes={self.axes!r}"
+        return f"PushMap(B={len(self)}, n={int(self.force.shape[1])}{tail})"
+
+    def weakest_push(self):
+        """Per walk the smallest critical push of any column and where it acts → (force [B],
+        step [B], axis [B]: 0 x or 1 y, sign [B]: +1 or −1).  A walk that fails unpushed gives
+        NaN, and one that no push topples +inf, both with step −1, axis −1 and sign 0."""
+        f = self.force
+        C = int(f.shape[2])
+        first = 1 if self.axes == "y" else 0  # the axis of columns 0 and 1
+        flat = f.reshape(f.shape[0], -1)
+        if hasattr(flat, "detach"):  # torch
+            import torch
+            nan = torch.isnan(flat)
+            filled = torch.where(nan, torch.full_like(flat, float("inf")), flat)
+            val, idx = filled.min(dim=1)
+            val = torch.where(nan.any(dim=1), torch.full_like(val, float("nan")), val)
+            none = ~torch.isfinite(val)
+            where, full = torch.where, torch.full_like
+            return (val, where(none, full(idx, -1), idx // C),
+                    where(none, full(idx, -1), first + (idx % C) // 2),
+                    where(none, full(idx, 0), 1 - 2 * (idx % 2)))
+        nan = np.isnan(flat)
+        filled = np.where(nan, np.inf, flat)
+        idx = filled.argmin(axis=1)
+        val = np.where(nan.any(axis=1), np.nan, filled[np.arange(flat.shape[0]), idx])
+        none = ~np.isfinite(val)
+        return (val, np.where(none, -1, idx // C), np.where(none, -1, first + (idx % C) // 2),
+                np.where(none, 0, 1 - 2 * (idx % 2)))
+
+    def rose(self, directions):
+        """Critical push magnitude along planar directions → (magnitude [B, n, K], limiting
+        sample [B, n, K]); directions [K, 2] vectors (dx, dy), normalised here.  Needs an "xy"
+        map; see planar_push."""
+        if self.axes != "xy":
+            raise ValueError(f"rose needs an 'xy' map, this one has axes = {self.axes!r}")
+        d = unit_directions(directions)
+        if d.ndim != 2:
+            raise ValueError(f"directions must be [K, 2], got shape {tuple(d.shape)}")
+        f, l = self.force, self.limit
+        return planar_push(f[:, :, None, :], l[:, :, None, :], d)
 
     def weakest(self):
         """Per walk the smallest critical push and where it acts → (force [B], step [B],
         direction [B]: +1 or −1).  A walk that fails unpushed gives NaN, and one that no push
-        topples +inf, both with step −1 and direction 0."""
+        topples +inf, both with step −1 and direction 0.  y-axis maps only (weakest_push takes
+        every map)."""
+        if self.axes != "y":
+            raise ValueError("weakest() reads a y-axis map; use weakest_push() for maps with an "
+                             "x axis")
         f = self.force
         flat = f.reshape(f.shape[0], -1)
         if hasattr(flat, "detach"):  # torch

@@ -25,7 +25,7 @@ from typing import Optional, Tuple
 import numpy as np
 import torch
 
-from ..analysis import NMETRICS, PushMap, WalkMetrics
+from ..analysis import NMETRICS, PushMap, WalkMetrics, planar_push, unit_directions
 from ..config import MPCConfig
 from ..models.lipm_model import lipm_matrices
 from ..solver import get_plan
@@ -457,7 +457,8 @@ class ZMPController:
         return plan, hist, zmax_t, zmin_t, lengths, B, n
 
     def push_map(self, z_max, z_min, x_init=None, walk_lengths=None,
-                 max_violation: float = 1e-9) -> PushMap:
+                 max_violation: float = 1e-9, duration: int = 1, profile=None,
+                 axes: str = "y") -> PushMap:
         """At which phase of the gait, and in which direction, is each walk weakest (addition;
         zmpc_push_map): one unpushed rollout, then the exact critical push of every (walk, push
         step, direction) in one launch — the F_ext sweep of run_compare_resistance.py:87-197 at
@@ -466,34 +467,57 @@ class ZMPController:
         force [B,n,2] in newtons ([..., 0] a +y push at that history step, [..., 1] a −y push,
         as zmp_controller.py:105-106 applies it), +inf where no sample limits the push (steps
         from n_b − 2 on), NaN for a walk that fails with no push; limit [B,n,2] the sample that
-        leaves its box first; weakest() the per-walk minimum.  Unconstrained plans only."""
+        leaves its box first; weakest() the per-walk minimum.  Unconstrained plans only.
+
+        duration, profile: a push that lasts `duration` samples from that history step on, with
+        force F·profile[j] in its j-th sample (None: constant); the entries are then the critical
+        F.  axes "x", "y" or "xy": the axis pushed — the columns are (+x, −x), (+y, −y) or
+        (+x, −x, +y, −y) (zmpc_push_map_shaped); PushMap.rose gives any planar direction from an
+        "xy" map, weakest_push() the per-walk minimum of every map."""
         plan, hist, zmax_t, zmin_t, lengths, _, _ = self._unpushed(z_max, z_min, x_init,
                                                                    walk_lengths)
         force, limit = plan.push_map(hist, zmax_t, zmin_t, lengths=lengths,
-                                     max_violation=max_violation, mass=self.config.m)
-        return PushMap(force, limit)
+                                     max_violation=max_violation, mass=self.config.m,
+                                     duration=duration, profile=profile, axes=axes)
+        return PushMap(force, limit, axes=axes)
 
     def critical_force_exact(self, z_max, z_min, x_init=None, force_step=None, direction=+1,
-                             max_violation: float = 1e-9, walk_lengths=None):
+                             max_violation: float = 1e-9, walk_lengths=None, duration: int = 1,
+                             profile=None):
         """critical_force's scenarios (same conventions and defaults: force_step defaults to
         n//2, or n_b//2 with walk_lengths; direction[b]·F newtons on the y axis) answered in
         closed form (addition; the single-step form of zmpc_push_map): one unpushed rollout and
         one launch instead of 32 pushed rollouts, a number instead of a bracket.  Returns [B]
         forces on the device: NaN where the walk fails with no push, +inf where no push at that
         step ever fails (critical_force reports its search limit there).  Only the ZMP criterion
-        (max_violation); raises on a strict plan."""
+        (max_violation); raises on a strict plan.
+
+        duration, profile: a sustained or shaped push as push_map.  direction may also hold
+        planar vectors (dx, dy), as a two-dimensional [1, 2] or [B, 2] array (a bare pair stays
+        two signs): the result is then the critical magnitude of a push along that direction,
+        from the x and y tables of one launch (analysis.planar_push)."""
+        planar = np.ndim(direction) == 2
+        if planar:
+            unit = unit_directions(direction)
+            # (K > 1 directions count as a [K] argument: one scenario each)
+            extra = (force_step,) + ((unit[:, 0],) if unit.shape[0] > 1 else ())
+        else:
+            extra = (force_step, direction)
         plan, hist, zmax_t, zmin_t, lengths, B, n = self._unpushed(
-            z_max, z_min, x_init, walk_lengths, extra=(force_step, direction))
+            z_max, z_min, x_init, walk_lengths, extra=extra)
         dev = hist.device
         if force_step is None:
             step = torch.full((B,), n // 2, dtype=torch.int64, device=dev) if lengths is None \
                 else lengths // 2
         else:
             step = torch.as_tensor(force_step, dtype=torch.int64, device=dev).expand(B)
-        force, _ = plan.push_map(hist, zmax_t, zmin_t, lengths=lengths,
-                                 push_steps=step.contiguous(), max_violation=max_violation,
-                                 mass=self.config.m)
-        sign = torch.as_tensor(direction, dtype=torch.float64, device=dev).expand(B)
+        force, limit = plan.push_map(hist, zmax_t, zmin_t, lengths=lengths,
+                                     push_steps=step.contiguous(), max_violation=max_violation,
+                                     mass=self.config.m, duration=duration, profile=profile,
+                                     axes="xy" if planar else "y")
+        if planar:
+            return planar_push(force, limit, unit)[0]
+        sign =torch.as_tensor(direction, dtype=torch.float64, device=dev).expand(B)
         return torch.where(sign >= 0, force[:, 0], force[:, 1])
 
     # ------------------------------------------------------------------ internals

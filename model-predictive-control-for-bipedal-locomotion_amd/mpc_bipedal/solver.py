@@ -287,10 +287,17 @@ class Plan:
 
     # -- push-robustness map (zmpc_push_map) -----------------------------------------------
     def push_map(self, hist, zmax, zmin, lengths=None, push_steps=None, max_violation=1e-9,
-                 out=None, want_response=False, *, mass):
+                 out=None, want_response=False, *, mass, duration=1, profile=None, axes="y"):
         """Exact critical push of every (walk, push step, direction) from an unpushed state
         history (zmpc_push_map, include/zmpc.h) → (force, limit) device tensors, with
         want_response=True (force, limit, response [n]).
+
+        duration, profile, axes (zmpc_push_map_shaped; at their defaults the call is
+        zmpc_push_map's): a push that lasts `duration` samples with force F·profile[j] during
+        history steps s + j (profile None: constant; a finite host array of `duration` weights,
+        or a float64 [duration] tensor on the plan's device, which is not inspected); axes "x",
+        "y" or "xy" — the last dimension of force and limit is then (+x, −x), (+y, −y) or
+        (+x, −x, +y, −y), and response is the shaped table.
 
         hist, zmax, zmin, lengths: as walk_metrics.  push_steps None: the full map, force float64
         and limit int32 [B, n, 2] ([..., 0] a +y push, [..., 1] a −y push at step s); push_steps
@@ -325,7 +332,22 @@ class Plan:
             steps_t = torch.as_tensor(push_steps, dtype=torch.int64, device=dev).contiguous()
             if tuple(steps_t.shape) != (B,):
                 raise ValueError(f"push_steps must be [B] = [{B}], got {tuple(steps_t.shape)}")
-        oshape = (B, n, 2) if steps_t is None else (B, 2)
+        from .analysis import AXES, check_profile
+        if axes not in AXES:
+            raise ValueError(f"axes must be 'x', 'y' or 'xy', got {axes!r}")
+        if isinstance(profile, torch.Tensor):
+            D, _ = check_profile(duration, None)
+            if profile.dtype != torch.float64 or profile.device != dev or \
+                    tuple(profile.shape) != (D,) or not profile.is_contiguous():
+                raise ValueError(f"a device profile must be a contiguous float64 [duration] = "
+                                 f"[{D}] tensor on the plan's device")
+            prof_t = profile
+        else:
+            D, w = check_profile(duration, profile)
+            prof_t = None if w is None else torch.as_tensor(w, device=dev)
+        shaped = D != 1 or prof_t is not None or axes != "y"
+        C = 4 if axes == "xy" else 2
+        oshape = (B, n, C) if steps_t is None else (B, C)
         if out is None:
             force = torch.empty(oshape, dtype=torch.float64, device=dev)
             limit = torch.empty(oshape, dtype=torch.int32, device=dev)
@@ -339,11 +361,17 @@ class Plan:
         resp = torch.empty(n, dtype=torch.float64, device=dev) if want_response else None
         with torch.cuda.device(self.device):
             stream = torch.cuda.current_stream(self.device).cuda_stream
-            rc = _native.load().zmpc_push_map(self._live(), B, n, _ptr(hist), _ptr(zmax),
-                                              _ptr(zmin), bstride, _ptr(len_t), _ptr(steps_t),
-                                              float(max_violation), float(mass), _ptr(force),
-                                              _ptr(limit), _ptr(resp), ctypes.c_void_p(stream))
-        _native.check(rc, "zmpc_push_map")
+            if shaped:
+                rc = _native.load().zmpc_push_map_shaped(
+                    self._live(), B, n, _ptr(hist), _ptr(zmax), _ptr(zmin), bstride, _ptr(len_t),
+                    _ptr(steps_t), _ptr(prof_t), D, AXES[axes], float(max_violation), float(mass),
+                    _ptr(force), _ptr(limit), _ptr(resp), ctypes.c_void_p(stream))
+            else:
+                rc = _native.load().zmpc_push_map(self._live(), B, n, _ptr(hist), _ptr(zmax),
+                                                  _ptr(zmin), bstride, _ptr(len_t), _ptr(steps_t),
+                                                  float(max_violation), float(mass), _ptr(force),
+                                                  _ptr(limit), _ptr(resp), ctypes.c_void_p(stream))
+        _native.check(rc, "zmpc_push_map_shaped" if shaped else "zmpc_push_map")
         return (force, limit, resp) if want_response else (force, limit)
 
     # -- fused rollout-to-metrics (zmpc_rollout_metrics) -----------------------------------
