@@ -353,8 +353,11 @@ int zmpc_push_map(const zmpc_plan* plan, int64_t B, int64_t n, const double* his
  * With axes = ZMPC_PUSH_AXIS_Y, D = 1 and a NULL profile, force, limit and response are
  * zmpc_push_map's bit for bit; a two-axis call equals the two one-axis calls column for column;
  * the single-step form returns the full map's rows bit for bit; two calls on the same input
- * agree bit for bit.  The shaped table is computed per call by a grid over the delays (n·min(D,
- * n)/2 products) into a stream-ordered workspace of 5n doubles.  In the full map the axes take
+ * agree bit for bit.  With D = 1 and a NULL profile the call is zmpc_push_map's on the axes
+ * asked for: no shaping launch, a stream-ordered workspace of 2n doubles.  Otherwise the shaped
+ * table is computed per call by a grid over the delays (n·min(D, n)/2 products) into a
+ * stream-ordered workspace of 5n doubles (a profile of one weight w_0 included: w_0
+ * multiplies).  In the full map the axes take
  * turns over the same LDS: n > 10112 returns ZMPC_ESTATE for one axis or two, with the limit in
  * the message; the single-step form takes any n.  A strict plan returns ZMPC_ESTATE.  Nothing
  * is launched on a refusal.  ZMPC_EINVAL before any device call: zmpc_push_map's cases,

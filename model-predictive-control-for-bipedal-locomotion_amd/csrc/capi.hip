@@ -442,36 +442,50 @@ int zmpc_rollout_metrics(const zmpc_plan* P, int64_t B, int64_t n, const double*
   return launch_result(e, std::string(), "zmpc_rollout_metrics");
 }
 
+// Both push-map entry points: `name` prefixes the messages; zmpc_push_map is the call with
+// duration 1, no profile and the y axis, under its own launch rule
+static int push_map_impl(const char* name, bool shaped, const zmpc_plan* P, const PushCall& c,
+                         void* stream) {
+  g_err.clear();
+  if (!P) return fail(ZMPC_EINVAL, "NULL plan");
+  if (c.B < 0 || c.n < 1) return fail(ZMPC_EINVAL, "need B >= 0 and n >= 1");
+  if (!(c.t >= 0)) return fail(ZMPC_EINVAL, "need max_violation >= 0");
+  if (!(c.mass > 0) || !(c.mass < __builtin_inf()))
+    return fail(ZMPC_EINVAL, "need a finite mass > 0");
+  if (c.bstride != 0 && c.bstride < 2 * c.n)
+    return fail(ZMPC_EINVAL, "bounds_stride must be 0 (shared CoP) or >= 2n");
+  if (c.duration < 1) return fail(ZMPC_EINVAL, "need duration >= 1 (samples)");
+  if (c.axes < 1 || c.axes > (ZMPC_PUSH_AXIS_X | ZMPC_PUSH_AXIS_Y))
+    return fail(ZMPC_EINVAL, "axes must be 1 (the x axis), 2 (the y axis) or 3 (both)");
+  if (c.B > 0 && (!c.hist || !c.zmax || !c.zmin || !c.force))
+    return fail(ZMPC_EINVAL, "NULL array argument");
+  if (c.B > 0x7fffffff) return fail(ZMPC_EINVAL, "batch too large");
+  if (c.n > (1 << 24)) return fail(ZMPC_EINVAL, "walk too long");
+  // refused before any device call, nothing is launched
+  if (P->strict)
+    return fail(ZMPC_ESTATE, std::string(name) +
+                                 ": the ZMP response of a strict (clamped) controller is not "
+                                 "affine in the push (bisect over pushed rollouts instead: "
+                                 "ZMPController.critical_force)");
+  const bool single = c.push_steps != nullptr;
+  const PushMapChoice k =
+      shaped ? choose_push_shaped(c.n, single, c.axes == 3 ? 2 : 1) : choose_push_map(c.n, single);
+  if (!k.ok) return fail(ZMPC_ESTATE, std::string(name) + ": " + k.why);
+  if (c.B == 0) return ZMPC_OK;
+  DeviceGuard g(P->device);
+  if (g.err != hipSuccess) return hip_fail(g.err, "hipSetDevice");
+  return launch_result(zmpc_launch_push_map(P, c, (hipStream_t)stream), std::string(), name);
+}
+
 int zmpc_push_map(const zmpc_plan* P, int64_t B, int64_t n, const double* hist,
                   const double* zmax, const double* zmin, int64_t bounds_stride,
                   const int64_t* lengths, const int64_t* push_steps, double max_violation,
                   double mass, double* force, int32_t* limit, double* response, void* stream) {
-  g_err.clear();
-  if (!P) return fail(ZMPC_EINVAL, "NULL plan");
-  if (B < 0 || n < 1) return fail(ZMPC_EINVAL, "need B >= 0 and n >= 1");
-  if (!(max_violation >= 0)) return fail(ZMPC_EINVAL, "need max_violation >= 0");
-  if (!(mass > 0) || !(mass < __builtin_inf()))
-    return fail(ZMPC_EINVAL, "need a finite mass > 0");
-  if (bounds_stride != 0 && bounds_stride < 2 * n)
-    return fail(ZMPC_EINVAL, "bounds_stride must be 0 (shared CoP) or >= 2n");
-  if (B > 0 && (!hist || !zmax || !zmin || !force))
-    return fail(ZMPC_EINVAL, "NULL array argument");
-  if (B > 0x7fffffff) return fail(ZMPC_EINVAL, "batch too large");
-  if (n > (1 << 24)) return fail(ZMPC_EINVAL, "walk too long");
-  // refused before any device call, nothing is launched
-  if (P->strict)
-    return fail(ZMPC_ESTATE, "zmpc_push_map: the ZMP response of a strict (clamped) controller "
-                             "is not affine in the push (bisect over pushed rollouts instead: "
-                             "ZMPController.critical_force)");
-  const PushMapChoice c = choose_push_map(n, push_steps != nullptr);
-  if (!c.ok) return fail(ZMPC_ESTATE, std::string("zmpc_push_map: ") + c.why);
-  if (B == 0) return ZMPC_OK;
-  DeviceGuard g(P->device);
-  if (g.err != hipSuccess) return hip_fail(g.err, "hipSetDevice");
-  const hipError_t e =
-      zmpc_launch_push_map(P, B, n, hist, zmax, zmin, bounds_stride, lengths, push_steps,
-                           max_violation, mass, force, limit, response, (hipStream_t)stream);
-  return launch_result(e, std::string(), "zmpc_push_map");
+  return push_map_impl("zmpc_push_map", false, P,
+                       PushCall{B, n, hist, zmax, zmin, bounds_stride, lengths, push_steps,
+                                nullptr, 1, ZMPC_PUSH_AXIS_Y, max_violation, mass, force, limit,
+                                response},
+                       stream);
 }
 
 int zmpc_push_map_shaped(const zmpc_plan* P, int64_t B, int64_t n, const double* hist,
@@ -479,35 +493,11 @@ int zmpc_push_map_shaped(const zmpc_plan* P, int64_t B, int64_t n, const double*
                          const int64_t* lengths, const int64_t* push_steps, const double* profile,
                          int64_t duration, int32_t axes, double max_violation, double mass,
                          double* force, int32_t* limit, double* response, void* stream) {
-  g_err.clear();
-  if (!P) return fail(ZMPC_EINVAL, "NULL plan");
-  if (B < 0 || n < 1) return fail(ZMPC_EINVAL, "need B >= 0 and n >= 1");
-  if (!(max_violation >= 0)) return fail(ZMPC_EINVAL, "need max_violation >= 0");
-  if (!(mass > 0) || !(mass < __builtin_inf()))
-    return fail(ZMPC_EINVAL, "need a finite mass > 0");
-  if (bounds_stride != 0 && bounds_stride < 2 * n)
-    return fail(ZMPC_EINVAL, "bounds_stride must be 0 (shared CoP) or >= 2n");
-  if (duration < 1) return fail(ZMPC_EINVAL, "need duration >= 1 (samples)");
-  if (axes < 1 || axes > (ZMPC_PUSH_AXIS_X | ZMPC_PUSH_AXIS_Y))
-    return fail(ZMPC_EINVAL, "axes must be 1 (the x axis), 2 (the y axis) or 3 (both)");
-  if (B > 0 && (!hist || !zmax || !zmin || !force))
-    return fail(ZMPC_EINVAL, "NULL array argument");
-  if (B > 0x7fffffff) return fail(ZMPC_EINVAL, "batch too large");
-  if (n > (1 << 24)) return fail(ZMPC_EINVAL, "walk too long");
-  // refused before any device call, nothing is launched
-  if (P->strict)
-    return fail(ZMPC_ESTATE, "zmpc_push_map_shaped: the ZMP response of a strict (clamped) "
-                             "controller is not affine in the push (bisect over pushed rollouts "
-                             "instead: ZMPController.critical_force)");
-  const PushMapChoice c = choose_push_shaped(n, push_steps != nullptr, axes == 3 ? 2 : 1);
-  if (!c.ok) return fail(ZMPC_ESTATE, std::string("zmpc_push_map_shaped: ") + c.why);
-  if (B == 0) return ZMPC_OK;
-  DeviceGuard g(P->device);
-  if (g.err != hipSuccess) return hip_fail(g.err, "hipSetDevice");
-  const hipError_t e = zmpc_launch_push_map_shaped(
-      P, B, n, hist, zmax, zmin, bounds_stride, lengths, push_steps, profile, duration, axes,
-      max_violation, mass, force, limit, response, (hipStream_t)stream);
-  return launch_result(e, std::string(), "zmpc_push_map_shaped");
+  return push_map_impl("zmpc_push_map_shaped", true, P,
+                       PushCall{B, n, hist, zmax, zmin, bounds_stride, lengths, push_steps,
+                                profile, duration, axes, max_violation, mass, force, limit,
+                                response},
+                       stream);
 }
 
 static int herdt_check(const zmpc_plan* P, const zmpc_herdt_params* prm, int64_t B) {

@@ -332,7 +332,7 @@ inline MetChoice choose_unc_metrics(int N, int64_t n, bool shared_cop, int opt_r
 }
 
 // ---------------------------------------------------------------------------------------------
-// Push-robustness map (zmpc_push_map; pushmap.hip)
+// Push-robustness maps (zmpc_push_map, zmpc_push_map_shaped; pushmap.hip)
 
 // The full map keeps a walk's (up, dn) margin pairs in LDS, 16 bytes per sample plus 64 pairs of
 // +inf behind them, one workgroup per walk.  Its dynamic-LDS ceiling is the wide kernel's 159 KiB

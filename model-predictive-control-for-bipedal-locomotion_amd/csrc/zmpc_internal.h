@@ -116,37 +116,30 @@ hipError_t zmpc_launch_walk_metrics(const zmpc_plan* p, int64_t B, int64_t n, co
                                     const double* zmax, const double* zmin, int64_t bstride,
                                     const int64_t* lengths, double* metrics, hipStream_t s);
 
-// push-robustness map of a state history (pushmap.hip): the shapes dispatch.h choose_push_map
-// takes (the caller refuses the others first) on a non-strict plan, whose kx, T, T²/2, T³/6 and
-// h/g it reads; t = max_violation; push_steps null: the full map, else the single-step form;
-// lengths, limit and response may be NULL.  hipErrorOutOfMemory: the response table's
-// stream-ordered workspace (2n doubles) could not be allocated
-hipError_t zmpc_launch_push_map(const zmpc_plan* p, int64_t B, int64_t n, const double* hist,
-                                const double* zmax, const double* zmin, int64_t bstride,
-                                const int64_t* lengths, const int64_t* push_steps, double t,
-                                double mass, double* force, int32_t* limit, double* response,
-                                hipStream_t s);
-// the two halves of zmpc_launch_push_map, for pushshaped.hip: the one-sample response of this n
-// into tab ([n] 16-byte pairs (r_d, 1/|r_d|)) and response ([n] doubles, may be NULL); and the map
-// or single-step kernels of zmpc_push_map on a table of that layout (B > 0)
-void zmpc_push_base_table(const zmpc_plan* p, int64_t n, double mass, void* tab, double* response,
-                          hipStream_t s);
-void zmpc_push_map_on_table(const zmpc_plan* p, int64_t B, int64_t n, const double* hist,
-                            const double* zmax, const double* zmin, int64_t bstride,
-                            const int64_t* lengths, const int64_t* push_steps, double t,
-                            const void* table, double* force, int32_t* limit, hipStream_t s);
-hipError_t zmpc_push_shaped_set_attrs();
+// The arguments of one zmpc_push_map / zmpc_push_map_shaped call (zmpc_push_map: duration 1, no
+// profile, the y axis).
+struct PushCall {
+  int64_t B, n;
+  const double *hist, *zmax, *zmin;
+  int64_t bstride;
+  const int64_t* lengths;     // may be null
+  const int64_t* push_steps;  // null: the full map, else the single-step form
+  const double* profile;      // device, [duration], may be null
+  int64_t duration;
+  int axes;  // ZMPC_PUSH_AXIS_X, _Y or both: force and limit hold 2 columns per step and axis
+  double t;  // max_violation
+  double mass;
+  double* force;
+  int32_t* limit;    // may be null
+  double* response;  // may be null
+};
 
-// the shaped and two-axis form (zmpc_push_map_shaped, pushshaped.hip): the shapes choose_push_shaped takes;
-// profile (device, [duration]) may be NULL; axes = ZMPC_PUSH_AXIS_X, _Y or both; force and limit
-// hold 2 columns per step and axis.  Workspace: 5n doubles
-hipError_t zmpc_launch_push_map_shaped(const zmpc_plan* p, int64_t B, int64_t n,
-                                       const double* hist, const double* zmax,
-                                       const double* zmin, int64_t bstride,
-                                       const int64_t* lengths, const int64_t* push_steps,
-                                       const double* profile, int64_t duration, int axes, double t,
-                                       double mass, double* force, int32_t* limit,
-                                       double* response, hipStream_t s);
+// push-robustness maps of a state history (pushmap.hip): the shapes dispatch.h choose_push_map /
+// choose_push_shaped take (the caller refuses the others first) on a non-strict plan, whose kx,
+// T, T²/2, T³/6 and h/g it reads.  hipErrorOutOfMemory: the response table's stream-ordered
+// workspace (2n doubles at duration 1 without a profile, which launches no shaping kernel; 5n
+// otherwise) could not be allocated
+hipError_t zmpc_launch_push_map(const zmpc_plan* p, const PushCall& c, hipStream_t s);
 hipError_t zmpc_push_map_set_attrs();
 
 // unconstrained rollout / step (rollout.hip)

@@ -16,7 +16,7 @@ history.  ``push_map_reference`` is that map in NumPy (again the checker, never 
 
 A push that lasts several samples, with or without a force profile, has the response
 ``shaped_response``; the x axis runs the same closed loop, and the axes decouple.
-``zmpc_push_map_shaped`` (``csrc/pushshaped.hip``) evaluates that on either axis or both,
+``zmpc_push_map_shaped`` (``csrc/pushmap.hip``) evaluates that on either axis or both,
 ``push_map_shaped_reference`` is its checker, and ``PushMap.weakest_push`` and ``PushMap.rose``
 (``planar_push``) read the columns (+x, −x, +y, −y), the latter along any planar direction.
 """

@@ -17,6 +17,18 @@ on prepared arguments, every round's time recorded:
   flip_route       today's only route to the x and y tables at D = 1: zmpc_push_map on y,
                    axis-flipped copies of the history and the bounds, zmpc_push_map again
                                                                                    (c) vs shaped_xy_d1
+  step_y           zmpc_push_map, single-step form at push_steps = n // 2 of every walk
+  step_x, step_xy  zmpc_push_map_shaped, axes = x / x | y, D = 1: the same single step
+
+Against another build of the library (it is named by ZMPC_LIB, one process per build and shape,
+in alternation, each into a directory of its own), then without a device:
+
+    python scripts/push_shaped_ab.py --out profiles/pushunit \
+        --compare-parent p1,p2,p3 --compare-new n1,n2,n3
+
+writes ab_vs_parent.json: per shape and form the median over processes of the per-process
+medians, the parent's own spread (largest − smallest of its process medians) / smallest, the
+ratio new / parent, and whether the ratio stays within 1 + spread.
 Shapes: config2 4096 walks, b1 one walk.  Reads no file outside the tree.  Needs a HIP device:
 there is no CPU path."""
 import argparse
@@ -76,16 +88,22 @@ def shape_record(name, c, zmax, zmin, B, rounds, launches, rng):
     def stream():
         return vp(torch.cuda.current_stream().cuda_stream)
 
-    def old(h, hi, lo, f, l):
+    steps = torch.full((B,), n // 2, dtype=torch.int64, device="cuda")
+    fs2, ls2 = torch.empty((B, 2), **f64), torch.empty((B, 2), dtype=torch.int32, device="cuda")
+    fs4, ls4 = torch.empty((B, 4), **f64), torch.empty((B, 4), dtype=torch.int32, device="cuda")
+
+    def old(h, hi, lo, f, l, st=None):
         rc = lib.zmpc_push_map(plan.handle, B, n, vp(h.data_ptr()), vp(hi.data_ptr()),
-                               vp(lo.data_ptr()), 2 * n, None, None, T_VIOL, cfg.m,
+                               vp(lo.data_ptr()), 2 * n, None,
+                               None if st is None else vp(st.data_ptr()), T_VIOL, cfg.m,
                                vp(f.data_ptr()), vp(l.data_ptr()), None, stream())
         if rc != 0:
             _native.check(rc, "zmpc_push_map")
 
-    def new(D, axes, f, l):
+    def new(D, axes, f, l, st=None):
         rc = lib.zmpc_push_map_shaped(plan.handle, B, n, vp(hist.data_ptr()), vp(zx.data_ptr()),
-                                      vp(zn.data_ptr()), 2 * n, None, None, None, D, axes, T_VIOL,
+                                      vp(zn.data_ptr()), 2 * n, None,
+                                      None if st is None else vp(st.data_ptr()), None, D, axes, T_VIOL,
                                       cfg.m, vp(f.data_ptr()), vp(l.data_ptr()), None, stream())
         if rc != 0:
             _native.check(rc, "zmpc_push_map_shaped")
@@ -103,7 +121,10 @@ def shape_record(name, c, zmax, zmin, B, rounds, launches, rng):
              "shaped_x_d1": lambda: new(1, 1, f2, l2),
              "shaped_xy_d1": lambda: new(1, 3, f4, l4),
              "shaped_xy_d20": lambda: new(20, 3, f4, l4),
-             "flip_route": flip_route}
+             "flip_route": flip_route,
+             "step_y": lambda: old(hist, zx, zn, fs2, ls2, steps),
+             "step_x": lambda: new(1, 1, fs2, ls2, steps),
+             "step_xy": lambda: new(1, 3, fs4, ls4, steps)}
     for fn in forms.values():  # warm-up of every form the timed window uses
         for _ in range(5):
             fn()
@@ -139,16 +160,45 @@ def shape_record(name, c, zmax, zmin, B, rounds, launches, rng):
             "c_flip_route_over_xy_d1": ratio("flip_route", "shaped_xy_d1")}
 
 
+def compare(parent_dirs, new_dirs, out):
+    """ab_vs_parent.json from the per-process records of two builds (no device)."""
+    res = {}
+    for shape in ("config2", "b1"):
+        def meds(dirs):
+            recs = [json.load(open(os.path.join(d, f"push_shaped_ab_{shape}.json"))) for d in dirs]
+            return {k: [r["ms"][k]["median"] for r in recs] for k in recs[0]["ms"]}
+        par, new = meds(parent_dirs), meds(new_dirs)
+        res[shape] = {}
+        for k in par:
+            mp, mn = float(np.median(par[k])), float(np.median(new[k]))
+            spread = (max(par[k]) - min(par[k])) / min(par[k])
+            res[shape][k] = {"parent_process_medians_ms": par[k], "new_process_medians_ms": new[k],
+                             "parent_ms": mp, "new_ms": mn, "parent_spread": spread,
+                             "new_over_parent": mn / mp,
+                             "within_parent_spread": bool(mn / mp <= 1.0 + spread)}
+    with open(os.path.join(out, "ab_vs_parent.json"), "w") as f:
+        json.dump(res, f, indent=1)
+    for shape, forms in res.items():
+        for k, v in forms.items():
+            print(f"{shape:8s} {k:14s} parent {v['parent_ms']:.4f} new {v['new_ms']:.4f} ms  "
+                  f"ratio {v['new_over_parent']:.3f}  spread {v['parent_spread']:.3f}  "
+                  f"{'ok' if v['within_parent_spread'] else 'SLOWER'}")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", required=True)
+    ap.add_argument("--compare-parent", default=None)
+    ap.add_argument("--compare-new", default=None)
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--launches", type=int, default=20)
     ap.add_argument("--only", choices=("config2", "b1"), default=None)
     args = ap.parse_args()
+    os.makedirs(args.out, exist_ok=True)
+    if args.compare_parent:
+        return compare(args.compare_parent.split(","), args.compare_new.split(","), args.out)
     if not torch.cuda.is_available():
         raise SystemExit("push_shaped_ab.py needs a HIP device (no CPU path)")
-    os.makedirs(args.out, exist_ok=True)
     c = ZMPController(MPCConfig(horizon=150, strict=False))
     walk = np.load(os.path.join(ROOT, "tests", "golden", "walk_n150.npz"))
     zmax, zmin = walk["zmax"], walk["zmin"]
