@@ -374,6 +374,61 @@ int zmpc_push_map_shaped(const zmpc_plan* plan, int64_t B, int64_t n, const doub
                          void* stream);
 
 /*
+ * Rollouts under shoves: pushes of any length, shape and direction, on every controller.  The
+ * reference can only disturb a walk the way zmp_controller.py:105-106 does it — one sample, the
+ * y axis, one velocity impulse (kick, kick_step) — and the push maps above answer sustained pushes
+ * for the unconstrained controller alone.
+ *
+ * The push, stated once.  Per walk b the inputs are a start step s_b, a duration D >= 1 shared by
+ * the batch, an optional profile w_0 .. w_(D−1), shared, on the device (NULL: all ones), and one
+ * amplitude per requested axis, amp[b, a] = dt·F_b·dir_(b,a)/m, in m/s.  For every history step i
+ * with j = i − s_b, 0 <= j < D and i < n − 1, the state of sample i + 1 on axis a has its
+ * velocity lowered by amp[b, a]·w_j.
+ *   - This is applied after x⁺ = A x + B u0, where the reference applies its kick.
+ *   - NULL profile: the velocity is lowered by amp[b, a] itself with no product, so D = 1
+ *     reproduces the kick's arithmetic.
+ *   - A start step outside [0, n − 1) means no push for that walk.
+ *   - A push that runs past the walk's end is truncated.
+ *   - An axis that was not requested is untouched, bit for bit.
+ *   - Sign: +F on an axis lowers that axis' velocity — the reference's y convention, mirrored for
+ *     x, as in zmpc_push_map_shaped.
+ *   - A non-finite weight gives unspecified values in the samples it reaches and never an
+ *     out-of-range access.
+ */
+typedef struct zmpc_push {
+  const double*  amp;       /* [B, C] device; C = 1 or 2 columns in the order of `axes` (x, y) */
+  int32_t        axes;      /* ZMPC_PUSH_AXIS_X | ZMPC_PUSH_AXIS_Y */
+  const int64_t* steps;     /* [B] device start steps, or NULL: `step` for every walk */
+  int64_t        step;
+  const double*  profile;   /* [duration] device, or NULL: ones */
+  int64_t        duration;  /* >= 1 */
+} zmpc_push;
+
+/*
+ * zmpc_rollout / zmpc_rollout_kicks under a push window; every other argument as there.
+ *   - The legacy push (axes = ZMPC_PUSH_AXIS_Y, duration 1, NULL profile) is zmpc_rollout_kicks
+ *     itself (zmpc_rollout with NULL steps) on every plan kind: hist and status bit for bit.
+ *   - Strict plans: the LQ and the parallel-in-time kernels (ZMPC_OPT_STRICT_SOLVER 0, 3, 4) take
+ *     the window in their time loop; ZMPC_OPT_KICK_ORDER sorts the walks by (start step, the
+ *     larger |amp| of the requested axes), and the results do not depend on the order.  The
+ *     reduced-Cholesky cross-checks (solvers 1 and 2) return ZMPC_ESTATE with the reason for
+ *     anything but the legacy push.
+ *   - Unconstrained plans: the closed loop is linear and time-invariant, so the call runs the
+ *     unpushed zmpc_rollout — any shape, any n — and then adds the state response
+ *         hist[b, s_b + d, a, :] −= amp[b, a]·Σ_{j <= min(D−1, d−1)} w_j·Ā^(d−j−1)·e1,  d >= 1
+ *     (the sum in ascending j, uncontracted; Ā = A − B·kxᵀ as zmpc_push_map) from a table computed
+ *     per call into a stream-ordered workspace of 4n doubles (8n with a profile or D > 1).  It
+ *     agrees with D + 1 chained restarts of zmpc_rollout to rounding; status is the unpushed
+ *     rollout's.
+ * ZMPC_EINVAL before any device call: NULL push, or NULL amp when B > 0; axes outside 1..3;
+ * duration < 1; zmpc_rollout's own cases.  B = 0 does nothing.  Nothing is launched on a refusal.
+ * Two calls on the same input agree bit for bit.  Additive to ABI 7.
+ */
+int zmpc_rollout_pushed(const zmpc_plan* plan, int64_t B, int64_t n, const double* zmax,
+                        const double* zmin, int64_t bounds_stride, const double* x0,
+                        const zmpc_push* push, double* hist, int32_t* status, void* stream);
+
+/*
  * Batched CoP-bound producer: CoPGenerator.generate_cop_trajectory
  * (generators/cop_generator.py:34-115) over the footstep plan of
  * generators/footstep_generator.py:19-49, one walk per set of parameters.
@@ -433,6 +488,21 @@ int zmpc_herdt_rollout(const zmpc_plan* plan, const zmpc_herdt_params* params, i
                        int64_t s_stride, const int32_t* nb_next, int64_t nb_stride,
                        const double* x0, const double* kick, int64_t kick_step, double* hist,
                        double* foot, int32_t* status, void* stream);
+
+/*
+ * zmpc_herdt_rollout under a push window (zmpc_push and "The push, stated once" above): the
+ * footstep-adapting controller under a shove of any length, shape and direction, with a start
+ * step per walk.  The window is applied in the (walk, axis) lane where the reference applies its
+ * impulse (:525-526).  The legacy push (axes = ZMPC_PUSH_AXIS_Y, duration 1, NULL profile, NULL
+ * steps) is zmpc_herdt_rollout's kick: hist, foot and status bit for bit.  ZMPC_EINVAL before any
+ * device call: NULL push, or NULL amp when B > 0; axes outside 1..3; duration < 1;
+ * zmpc_herdt_rollout's own cases.  B = 0 does nothing.  Additive to ABI 7.
+ */
+int zmpc_herdt_rollout_pushed(const zmpc_plan* plan, const zmpc_herdt_params* params, int64_t B,
+                              int64_t n, const double* v_ref, int64_t v_stride,
+                              const int8_t* states, int64_t s_stride, const int32_t* nb_next,
+                              int64_t nb_stride, const double* x0, const zmpc_push* push,
+                              double* hist, double* foot, int32_t* status, void* stream);
 
 /*
  * Batched predict_herdt_joint (zmp_controller.py:533-826), one QP per instance, cold start:

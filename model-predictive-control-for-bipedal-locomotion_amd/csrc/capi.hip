@@ -345,10 +345,41 @@ int zmpc_step(const zmpc_plan* P, int64_t B, const double* x, const double* zmax
   return launch_result(e, why, "zmpc_step");
 }
 
+// The checks of a zmpc_push (include/zmpc.h "The push, stated once"), before any device call
+static int push_check(const zmpc_push* push, int64_t B) {
+  if (!push) return fail(ZMPC_EINVAL, "push is NULL");
+  if (push->axes < 1 || push->axes > (ZMPC_PUSH_AXIS_X | ZMPC_PUSH_AXIS_Y))
+    return fail(ZMPC_EINVAL, "push axes must be 1 (the x axis), 2 (the y axis) or 3 (both)");
+  if (push->duration < 1) return fail(ZMPC_EINVAL, "need push duration >= 1 (samples)");
+  if (B > 0 && !push->amp) return fail(ZMPC_EINVAL, "push amp is NULL");
+  return ZMPC_OK;
+}
+
+// the legacy push: one sample on y without a profile, the kick of zmpc_rollout itself
+static bool push_is_kick(const zmpc_push* push) {
+  return push->axes == ZMPC_PUSH_AXIS_Y && push->duration == 1 && push->profile == nullptr;
+}
+
+// A checked zmpc_push as the launchers take it, in a walk of n samples
+static PushArgs push_args(const zmpc_push* push, int64_t n) {
+  PushArgs w{};
+  w.amp = push->amp;
+  w.w = push->profile;
+  w.steps = push->steps;
+  w.step = push->step;
+  w.dur = (int)(push->duration < n ? push->duration : n);
+  w.cols = push->axes == (ZMPC_PUSH_AXIS_X | ZMPC_PUSH_AXIS_Y) ? 2 : 1;
+  w.col[0] = (push->axes & ZMPC_PUSH_AXIS_X) ? 0 : -1;
+  w.col[1] = (push->axes & ZMPC_PUSH_AXIS_Y) ? w.cols - 1 : -1;
+  return w;
+}
+
+// zmpc_rollout, zmpc_rollout_kicks and, with a push window (kick is NULL then), the general
+// zmpc_rollout_pushed
 static int rollout_impl(const zmpc_plan* P, int64_t B, int64_t n, const double* zmax,
                         const double* zmin, int64_t bounds_stride, const double* x0,
                         const double* kick, int64_t kick_step, const int64_t* kick_steps,
-                        double* hist, int32_t* status, void* stream) {
+                        const zmpc_push* push, double* hist, int32_t* status, void* stream) {
   g_err.clear();
   if (!P) return fail(ZMPC_EINVAL, "NULL plan");
   if (B < 0 || n < 1) return fail(ZMPC_EINVAL, "need B >= 0 and n >= 1");
@@ -358,23 +389,47 @@ static int rollout_impl(const zmpc_plan* P, int64_t B, int64_t n, const double* 
   if (n > (1 << 24)) return fail(ZMPC_EINVAL, "walk too long");
   if (bounds_stride != 0 && bounds_stride < 2 * n)
     return fail(ZMPC_EINVAL, "bounds_stride must be 0 (shared CoP) or >= 2n");
+  if (push && P->strict) {
+    // refused before any device call, nothing is launched
+    const StrictKind kind =
+        choose_strict(P->N, 2 * B, P->opt[ZMPC_OPT_STRICT_SOLVER], P->lqtab != nullptr);
+    if (kind == StrictKind::Tile && P->opt[ZMPC_OPT_STRICT_SOLVER] == 0)
+      return fail(ZMPC_ESTATE,
+                  "zmpc_rollout_pushed: at horizon N = " + std::to_string(P->N) +
+                      " neither the LQ nor the parallel-in-time strict kernel runs, and the "
+                      "reduced-Cholesky kernel left takes the one-sample y push alone");
+    if (kind == StrictKind::Tile || kind == StrictKind::Wave)
+      return fail(ZMPC_ESTATE,
+                  "zmpc_rollout_pushed: the reduced-Cholesky strict kernels (strict solver options "
+                  "1 and 2) take the one-sample y push alone (the y axis, duration 1, no profile); "
+                  "use strict solver 0, 3 or 4");
+  }
   DeviceGuard g(P->device);
   if (g.err != hipSuccess) return hip_fail(g.err, "hipSetDevice");
   std::string why;
   hipStream_t s = (hipStream_t)stream;
-  const RolloutCall c{B, n, zmax, zmin, bounds_stride, x0, kick, kick_step, kick_steps, hist,
-                      status};
-  hipError_t e = P->strict ? zmpc_launch_rollout_strict(P, c, s, &why)
-                           : zmpc_launch_rollout_unc(P, c, s, &why);
-  return launch_result(e, why, "zmpc_rollout");
+  RolloutCall c{B, n, zmax, zmin, bounds_stride, x0, kick, kick_step, kick_steps, hist, status};
+  hipError_t e;
+  if (P->strict) {
+    if (push) c.push = push_args(push, n);
+    e = zmpc_launch_rollout_strict(P, c, s, &why);
+  } else {
+    // (unconstrained: the unpushed rollout, then the window's linear state response)
+    e = zmpc_launch_rollout_unc(P, c, s, &why);
+    if (push && e == hipSuccess) {
+      c.push = push_args(push, n);
+      e = zmpc_launch_push_response(P, c, s);
+    }
+  }
+  return launch_result(e, why, push ? "zmpc_rollout_pushed" : "zmpc_rollout");
 }
 
 int zmpc_rollout(const zmpc_plan* P, int64_t B, int64_t n, const double* zmax,
                  const double* zmin, int64_t bounds_stride, const double* x0,
                  const double* kick, int64_t kick_step, double* hist, int32_t* status,
                  void* stream) {
-  return rollout_impl(P, B, n, zmax, zmin, bounds_stride, x0, kick, kick_step, nullptr, hist,
-                      status, stream);
+  return rollout_impl(P, B, n, zmax, zmin, bounds_stride, x0, kick, kick_step, nullptr, nullptr,
+                      hist, status, stream);
 }
 
 int zmpc_rollout_kicks(const zmpc_plan* P, int64_t B, int64_t n, const double* zmax,
@@ -385,7 +440,21 @@ int zmpc_rollout_kicks(const zmpc_plan* P, int64_t B, int64_t n, const double* z
     g_err.clear();
     return fail(ZMPC_EINVAL, "kick_steps is NULL (use zmpc_rollout for one kick step)");
   }
-  return rollout_impl(P, B, n, zmax, zmin, bounds_stride, x0, kick, -1, kick_steps, hist,
+  return rollout_impl(P, B, n, zmax, zmin, bounds_stride, x0, kick, -1, kick_steps, nullptr, hist,
+                      status, stream);
+}
+
+int zmpc_rollout_pushed(const zmpc_plan* P, int64_t B, int64_t n, const double* zmax,
+                        const double* zmin, int64_t bounds_stride, const double* x0,
+                        const zmpc_push* push, double* hist, int32_t* status, void* stream) {
+  g_err.clear();
+  if (!P) return fail(ZMPC_EINVAL, "NULL plan");
+  const int rc = push_check(push, B);
+  if (rc != ZMPC_OK) return rc;
+  if (push_is_kick(push))  // what users get today, on every plan kind
+    return rollout_impl(P, B, n, zmax, zmin, bounds_stride, x0, push->amp,
+                        push->steps ? -1 : push->step, push->steps, nullptr, hist, status, stream);
+  return rollout_impl(P, B, n, zmax, zmin, bounds_stride, x0, nullptr, -1, nullptr, push, hist,
                       status, stream);
 }
 
@@ -515,12 +584,13 @@ static int herdt_check(const zmpc_plan* P, const zmpc_herdt_params* prm, int64_t
   return ZMPC_OK;
 }
 
-int zmpc_herdt_rollout(const zmpc_plan* P, const zmpc_herdt_params* prm, int64_t B, int64_t n,
-                       const double* v_ref, int64_t v_stride, const int8_t* states,
-                       int64_t s_stride, const int32_t* nb_next, int64_t nb_stride,
-                       const double* x0, const double* kick, int64_t kick_step, double* hist,
-                       double* foot, int32_t* status, void* stream) {
-  g_err.clear();
+// zmpc_herdt_rollout and, with a push window (kick is NULL then), zmpc_herdt_rollout_pushed
+static int herdt_rollout_impl(const zmpc_plan* P, const zmpc_herdt_params* prm, int64_t B,
+                              int64_t n, const double* v_ref, int64_t v_stride,
+                              const int8_t* states, int64_t s_stride, const int32_t* nb_next,
+                              int64_t nb_stride, const double* x0, const double* kick,
+                              int64_t kick_step, const zmpc_push* push, double* hist, double* foot,
+                              int32_t* status, void* stream) {
   int rc = herdt_check(P, prm, B);
   if (rc != ZMPC_OK) return rc;
   if (n < 1) return fail(ZMPC_EINVAL, "need n >= 1");
@@ -540,9 +610,36 @@ int zmpc_herdt_rollout(const zmpc_plan* P, const zmpc_herdt_params* prm, int64_t
   }
   std::string why;
   hipError_t e = zmpc_launch_herdt(P, prm, B, n, 0, v_ref, v_stride, states, s_stride, nb_next,
-                                   nb_stride, x0, kick, kick_step, nullptr, nullptr, nullptr,
-                                   hist, foot, status, s, &why);
-  return launch_result(e, why, "zmpc_herdt_rollout");
+                                   nb_stride, x0, kick, kick_step,
+                                   push ? push_args(push, n) : PushArgs{}, nullptr, nullptr,
+                                   nullptr, hist, foot, status, s, &why);
+  return launch_result(e, why, push ? "zmpc_herdt_rollout_pushed" : "zmpc_herdt_rollout");
+}
+
+int zmpc_herdt_rollout(const zmpc_plan* P, const zmpc_herdt_params* prm, int64_t B, int64_t n,
+                       const double* v_ref, int64_t v_stride, const int8_t* states,
+                       int64_t s_stride, const int32_t* nb_next, int64_t nb_stride,
+                       const double* x0, const double* kick, int64_t kick_step, double* hist,
+                       double* foot, int32_t* status, void* stream) {
+  g_err.clear();
+  return herdt_rollout_impl(P, prm, B, n, v_ref, v_stride, states, s_stride, nb_next, nb_stride,
+                            x0, kick, kick_step, nullptr, hist, foot, status, stream);
+}
+
+int zmpc_herdt_rollout_pushed(const zmpc_plan* P, const zmpc_herdt_params* prm, int64_t B,
+                              int64_t n, const double* v_ref, int64_t v_stride,
+                              const int8_t* states, int64_t s_stride, const int32_t* nb_next,
+                              int64_t nb_stride, const double* x0, const zmpc_push* push,
+                              double* hist, double* foot, int32_t* status, void* stream) {
+  g_err.clear();
+  if (!P || !prm) return fail(ZMPC_EINVAL, "NULL plan or params");
+  const int rc = push_check(push, B);
+  if (rc != ZMPC_OK) return rc;
+  if (push_is_kick(push) && !push->steps)  // what users get today
+    return herdt_rollout_impl(P, prm, B, n, v_ref, v_stride, states, s_stride, nb_next, nb_stride,
+                              x0, push->amp, push->step, nullptr, hist, foot, status, stream);
+  return herdt_rollout_impl(P, prm, B, n, v_ref, v_stride, states, s_stride, nb_next, nb_stride,
+                            x0, nullptr, -1, push, hist, foot, status, stream);
 }
 
 int zmpc_herdt_step(const zmpc_plan* P, const zmpc_herdt_params* prm, int64_t B,
@@ -560,8 +657,8 @@ int zmpc_herdt_step(const zmpc_plan* P, const zmpc_herdt_params* prm, int64_t B,
   if (g.err != hipSuccess) return hip_fail(g.err, "hipSetDevice");
   std::string why;
   hipError_t e = zmpc_launch_herdt(P, prm, B, 1, 1, v_win, 2 * (int64_t)P->N, s_win, P->N,
-                                   nullptr, 0, x, nullptr, -1, current, foot, side, x_next, step,
-                                   status, (hipStream_t)stream, &why);
+                                   nullptr, 0, x, nullptr, -1, PushArgs{}, current, foot, side,
+                                   x_next, step, status, (hipStream_t)stream, &why);
   return launch_result(e, why, "zmpc_herdt_step");
 }
 

@@ -86,6 +86,7 @@ struct HerdtArgs {
   int maxit;                // active-set pass cap per solve (ZMPC_ST_MAXITER beyond)
   unsigned long long* prof; // diagnostics build only (ZMPC_DIAG, ZMPC_HERDT_PROF): clock per
                             // phase, summed; null in the product library
+  PushArgs push;            // the push window of zmpc_herdt_rollout_pushed; all zero: the kick above
 };
 
 // Slab row k (4 doubles, written by sweep 2, read by the forward sweep):
@@ -492,8 +493,11 @@ __global__ void __launch_bounds__(64) zmpc_herdt_kernel(HerdtArgs a) {
   unsigned long long pr_b = 0, pr_f = 0, pr_w = 0, pr_t0 = (kProf && a.prof) ? clock64() : 0;
   unsigned long long pr_kw = 0, pr_ns = 0, pr_own = 0, pr_fs = 0, pr_lw = 0;
   const int64_t nsteps = a.window_mode ? 1 : a.n - 1;
-  const int64_t kstep = (!a.window_mode && axis == 1 && a.kick) ? a.kick_step : -1;
-  const double kv = (kstep >= 0 && valid) ? a.kick[wc] : 0.0;
+  // the lane's push window: steps [kstep, kstep + pdur) (zmpc.h "The push, stated once"; the
+  // legacy kick is the window of one step on y)
+  const double* const pamp = a.window_mode ? nullptr : push_amp(a.push, a.kick, wc, axis);
+  const int kstep = pamp ? push_start(a.push, nullptr, a.kick_step, wc, a.n) : kNoPush;
+  const unsigned pdur = push_dur(a.push);
 
   for (int64_t i = 0; i < nsteps; ++i) {
     // ---- window of this timestep: states, segments, constraint kinds (:561-573, :687-712)
@@ -931,7 +935,9 @@ __global__ void __launch_bounds__(64) zmpc_herdt_kernel(HerdtArgs a) {
       fc = (m > 0) ? f0 : air;
       air = fc;
     }
-    if (i == kstep) xn[1] -= kv;  // F_ext impulse on the y state (:525-526)
+    // F_ext impulse on the state (:525-526), over the window's steps
+    if ((unsigned)((int)i - kstep) < pdur)
+      xn[1] -= push_value(a.push, pamp, (unsigned)((int)i - kstep));
     if (nxt != cur) cur = nxt;
     x[0] = xn[0];
     x[1] = xn[1];
@@ -995,9 +1001,9 @@ hipError_t zmpc_launch_herdt(const zmpc_plan* p, const zmpc_herdt_params* prm, i
                              int64_t n, int window_mode, const double* vref, int64_t vs,
                              const int8_t* st, int64_t ss, const int32_t* nb, int64_t ns,
                              const double* x0, const double* kick, int64_t kick_step,
-                             const int8_t* cur0, const double* fc0, const int8_t* side0,
-                             double* hist, double* foot, int32_t* status, hipStream_t s,
-                             std::string* why) {
+                             const PushArgs& push, const int8_t* cur0, const double* fc0,
+                             const int8_t* side0, double* hist, double* foot, int32_t* status,
+                             hipStream_t s, std::string* why) {
   HerdtArgs a{};
   a.N = p->N;
   a.window_mode = window_mode;
@@ -1030,6 +1036,7 @@ hipError_t zmpc_launch_herdt(const zmpc_plan* p, const zmpc_herdt_params* prm, i
   a.x0 = x0;
   a.kick = kick;
   a.kick_step = kick_step;
+  a.push = push;
   a.cur0 = cur0;
   a.fc0 = fc0;
   a.side0 = side0;

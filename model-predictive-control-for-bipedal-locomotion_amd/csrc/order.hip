@@ -17,17 +17,25 @@
 namespace {
 
 // Sort key: kick step (−1: none) in the high word, the kick as an order-preserving 32-bit image
-// of its float value in the low word (a scheduling key, so float precision is plenty).
+// of its float value in the low word (a scheduling key, so float precision is plenty).  A push
+// window (push.amp set) sorts by its start step and the larger |amp| of its axes.
 __global__ void __launch_bounds__(256) zmpc_kick_key_kernel(const double* __restrict__ kick,
                                                             const int64_t* __restrict__ ksteps,
-                                                            int64_t kstep, int64_t B,
+                                                            int64_t kstep, PushArgs push, int64_t B,
                                                             unsigned long long* keys,
                                                             int32_t* idx) {
   const int64_t b = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (b >= B) return;
-  const int64_t ks = ksteps ? ksteps[b] : kstep;
+  const int64_t ks = push.amp ? (push.steps ? push.steps[b] : push.step)
+                              : (ksteps ? ksteps[b] : kstep);
   const unsigned hi = (unsigned)(ks < 0 ? 0 : (ks >= 0x7fffffff ? 0x7fffffff : ks + 1));
-  const float kf = (float)kick[b];
+  float kf;
+  if (push.amp) {
+    kf = fabsf((float)push.amp[b * push.cols]);
+    if (push.cols == 2) kf = fmaxf(kf, fabsf((float)push.amp[b * 2 + 1]));
+  } else {
+    kf = (float)kick[b];
+  }
   unsigned u = __float_as_uint(kf == 0.0f ? 0.0f : kf);  // −0 → +0
   u = (u & 0x80000000u) ? ~u : (u | 0x80000000u);       // IEEE order → unsigned order
   keys[b] = ((unsigned long long)hi << 32) | u;
@@ -46,7 +54,8 @@ size_t zmpc_kick_order_bytes(int64_t B) {
 }
 
 hipError_t zmpc_kick_order(const double* kick, const int64_t* kick_steps, int64_t kick_step,
-                           int64_t B, int32_t* perm, void* ws, hipStream_t s) {
+                           const PushArgs& push, int64_t B, int32_t* perm, void* ws,
+                           hipStream_t s) {
   size_t tmp = 0;
   hipError_t e = hipcub::DeviceRadixSort::SortPairs(
       nullptr, tmp, (const unsigned long long*)nullptr, (unsigned long long*)nullptr,
@@ -58,7 +67,7 @@ hipError_t zmpc_kick_order(const double* kick, const int64_t* kick_steps, int64_
   auto* iin = reinterpret_cast<int32_t*>(kout + B);
   void* t = reinterpret_cast<void*>(((uintptr_t)(iin + B) + 255) & ~(uintptr_t)255);
   hipLaunchKernelGGL(zmpc_kick_key_kernel, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, s,
-                     kick, kick_steps, kick_step, B, kin, iin);
+                     kick, kick_steps, kick_step, push, B, kin, iin);
   if ((e = hipGetLastError()) != hipSuccess) return e;
   return hipcub::DeviceRadixSort::SortPairs(t, tmp, kin, kout, iin, perm, (int)B, 0, 64, s);
 }

@@ -27,6 +27,10 @@
 // single-step form, one wave per walk with lanes over samples and a min-butterfly as metrics.hip
 // MetAcc.
 //
+// The same unit serves zmpc_rollout_pushed on unconstrained plans (the push itself rolled out): the
+// response kernel also emits the state response Ā^(d−1)·e1, zmpc_push_state_shape_kernel sums it
+// over a push window and zmpc_push_add_kernel streams it onto an unpushed history (further down).
+//
 // What makes every form agree with every other bit for bit (two axes with one axis column for
 // column, the single-step form with the map's rows, a launch with its repetition):
 //   - all candidates come from push_cand and push_pair, uncontracted (fp contract off);
@@ -52,6 +56,8 @@ struct ipair_t {
 
 // Walks per workgroup of the single-step kernel (one wave each)
 constexpr int kStepWaves = 4;
+// Delays per workgroup of the shaping kernels
+constexpr int kShapeThreads = 256;
 
 // ---------------------------------------------------------------------------------------------
 // Response table: tab[d] = (r_d, q_d = 1/|r_d|) (q_d = 0 where r_d = 0), one 16-byte scalar load
@@ -71,10 +77,13 @@ __device__ __forceinline__ void matvec(const Mat3& m, double v[3]) {
   v[2] = z;
 }
 
+//
+// vec (may be null, as may tab) receives the state response itself for zmpc_rollout_pushed: vec[d]
+// = (Ā^(d−1)·e1, 0) as two 16-byte pairs, vec[0] = 0 — the same per-lane powers and squarings.
 __global__ void __launch_bounds__(64)
 zmpc_push_response_kernel(int64_t n, const double* __restrict__ kx, double T, double T2_2,
                           double T3_6, double hg, double dtm, pair_t* __restrict__ tab,
-                          double* __restrict__ resp) {
+                          double* __restrict__ resp, pair_t* __restrict__ vec) {
   const int lane = threadIdx.x;
   const double k0 = kx[0], k1 = kx[1], k2 = kx[2];
   Mat3 A;  // Ā = A − B·kxᵀ
@@ -101,15 +110,92 @@ zmpc_push_response_kernel(int64_t n, const double* __restrict__ kx, double T, do
     M = S;
   }
   if (lane == 0) {
-    tab[0] = pair_t{0.0, 0.0};
+    if (tab) tab[0] = pair_t{0.0, 0.0};
     if (resp) resp[0] = 0.0;
+    if (vec) vec[0] = vec[1] = pair_t{0.0, 0.0};
   }
   for (int64_t d = 1 + lane; d < n; d += 64) {
     // d = 1: C·e1 = 0 exactly
     const double r = d == 1 ? 0.0 : -dtm * (v[0] - hg * v[2]);
-    tab[d] = pair_t{r, r == 0.0 ? 0.0 : 1.0 / fabs(r)};
+    if (tab) tab[d] = pair_t{r, r == 0.0 ? 0.0 : 1.0 / fabs(r)};
     if (resp) resp[d] = r;
+    if (vec) {
+      vec[2 * d] = pair_t{v[0], v[1]};
+      vec[2 * d + 1] = pair_t{v[2], 0.0};
+    }
     matvec(M, v);
+  }
+}
+
+// ---------------------------------------------------------------------------------------------
+// zmpc_rollout_pushed on an unconstrained plan: the closed loop is linear and time-invariant, so
+// the pushed history is the unpushed one plus the state response of the window,
+//     hist[b, s_b + d, a, :] −= amp[b, a]·S_d,   S_d = Σ_{j = 0}^{min(D−1, d−1)} w_j·Ā^(d−j−1)·e1
+// for d >= 1 (the velocity of sample s + j + 1 is lowered by amp·w_j and travels on under Ā).
+//
+// Shaping: S_d from the table vec of the response kernel, a grid over delays as
+// zmpc_push_shape_kernel (the weight wave-uniform, ascending j, no product without a profile).
+__global__ void __launch_bounds__(kShapeThreads)
+zmpc_push_state_shape_kernel(int64_t n, const pair_t* __restrict__ vec,
+                             const double* __restrict__ w, int64_t D, pair_t* __restrict__ out) {
+  const int64_t d = (int64_t)blockIdx.x * kShapeThreads + threadIdx.x;
+  const int64_t dwave = __builtin_amdgcn_readfirstlane((int)(d | 63));
+  const int64_t dlast = dwave < n - 1 ? dwave : n - 1;
+  const int64_t jend = D - 1 < dlast - 1 ? D - 1 : dlast - 1;
+  const bool live = d < n;
+  double a0 = 0.0, a1 = 0.0, a2 = 0.0;
+  for (int64_t j = 0; j <= jend; ++j) {
+    const double wj = w ? w[j] : 1.0;
+    if (live && j < d) {
+      const pair_t p = vec[2 * (d - j)], q = vec[2 * (d - j) + 1];
+      a0 += w ? wj * p.x : p.x;
+      a1 += w ? wj * p.y : p.y;
+      a2 += w ? wj * q.x : q.x;
+    }
+  }
+  if (live) {
+    out[2 * d] = pair_t{a0, a1};
+    out[2 * d + 1] = pair_t{a2, 0.0};
+  }
+}
+
+// Adding: a walk's history is 3n 16-byte pairs, (c, ċ)x (c̈x, cy) (ċ, c̈)y per sample; consecutive
+// lanes take consecutive pairs from the first pushed sample s_b + 1 on (one coalesced 16-byte load
+// and store each; the table's 32 bytes per delay come from cache).  The workgroups of a walk
+// stride over its pairs; a walk whose start step lies outside [0, n − 1) is left alone, and a pair
+// no pushed axis reaches is neither read nor written.  cx, cy: the column of an axis in amp, −1
+// for an axis that is not pushed.
+constexpr int kAddThreads = 256;
+
+__global__ void __launch_bounds__(kAddThreads)
+zmpc_push_add_kernel(int64_t n, int chunks, const double* __restrict__ amp, int cols, int cx,
+                     int cy, const int64_t* __restrict__ steps, int64_t step,
+                     const pair_t* __restrict__ S, double* __restrict__ hist) {
+  const int64_t b = blockIdx.x / (unsigned)chunks;
+  const int chunk = (int)(blockIdx.x % (unsigned)chunks);
+  const int64_t s = steps ? steps[b] : step;
+  if (s < 0 || s >= n - 1) return;
+  const double ax = cx >= 0 ? amp[b * cols + cx] : 0.0;
+  const double ay = cy >= 0 ? amp[b * cols + cy] : 0.0;
+  pair_t* h = reinterpret_cast<pair_t*>(hist + b * n * 6);
+  const int p0 = 3 * ((int)s + 1), p1 = 3 * (int)n;  // (n <= 2^24)
+  for (int p = p0 + chunk * kAddThreads + (int)threadIdx.x; p < p1; p += chunks * kAddThreads) {
+    const int i = p / 3, m = p - 3 * i;
+    if ((m == 0 && cx < 0) || (m == 2 && cy < 0)) continue;
+    const int d = i - (int)s;
+    const pair_t u = S[2 * d], v = S[2 * d + 1];  // (S0, S1), (S2, 0)
+    pair_t e = h[p];
+    if (m == 0) {
+      e.x -= ax * u.x;
+      e.y -= ax * u.y;
+    } else if (m == 1) {
+      if (cx >= 0) e.x -= ax * v.x;
+      if (cy >= 0) e.y -= ay * u.x;
+    } else {
+      e.x -= ay * u.y;
+      e.y -= ay * v.x;
+    }
+    h[p] = e;
   }
 }
 
@@ -119,8 +205,6 @@ zmpc_push_response_kernel(int64_t n, const double* __restrict__ kx, double T, do
 // load) and consecutive lanes read consecutive r; a lane past its own delay skips the term.  A
 // term with r = 0 is skipped (no 0·inf from a non-finite weight; R_0 = R_1 = 0 whatever w), and w
 // null skips the product.  w is read at j <= min(D, n) − 1 only.
-constexpr int kShapeThreads = 256;
-
 __global__ void __launch_bounds__(kShapeThreads)
 zmpc_push_shape_kernel(int64_t n, const double* __restrict__ r, const double* __restrict__ w,
                        int64_t D, pair_t* __restrict__ tab, double* __restrict__ resp) {
@@ -417,7 +501,7 @@ hipError_t zmpc_launch_push_map(const zmpc_plan* p, const PushCall& c, hipStream
   pair_t* tab = shape ? ws + n : ws;
   double* base = shape ? reinterpret_cast<double*>(ws + 2 * n) : c.response;
   hipLaunchKernelGGL(zmpc_push_response_kernel, dim3(1), dim3(64), 0, s, n, p->kx, p->T, p->T2_2,
-                     p->T3_6, p->hg, p->T / c.mass, ws, base);
+                     p->T3_6, p->hg, p->T / c.mass, ws, base, (pair_t*)nullptr);
   if (shape)
     hipLaunchKernelGGL(zmpc_push_shape_kernel,
                        dim3((unsigned)((n + kShapeThreads - 1) / kShapeThreads)),
@@ -439,6 +523,36 @@ hipError_t zmpc_launch_push_map(const zmpc_plan* p, const PushCall& c, hipStream
                          c.zmin, c.bstride, c.lengths, p->hg, c.t, tab, axis, c.force, c.limit);
     }
   }
+  e = hipGetLastError();
+  const hipError_t ef = hipFreeAsync(ws, s);
+  return e != hipSuccess ? e : ef;
+}
+
+hipError_t zmpc_launch_push_response(const zmpc_plan* p, const RolloutCall& c, hipStream_t s) {
+  const int64_t n = c.n, B = c.B;
+  const PushArgs& w = c.push;
+  if (n < 2 || B < 1) return hipSuccess;  // no step to push at
+  const bool shape = w.dur != 1 || w.w != nullptr;
+  // the state response of this n, recomputed per launch into one stream-ordered workspace: two
+  // pairs per delay, and as many again for the shaped table
+  pair_t* ws = nullptr;
+  hipError_t e = hipMallocAsync((void**)&ws, (size_t)n * (shape ? 4 : 2) * sizeof(pair_t), s);
+  if (e != hipSuccess) return hipErrorOutOfMemory;
+  hipLaunchKernelGGL(zmpc_push_response_kernel, dim3(1), dim3(64), 0, s, n, p->kx, p->T, p->T2_2,
+                     p->T3_6, p->hg, 0.0, (pair_t*)nullptr, (double*)nullptr, ws);
+  const pair_t* S = ws;
+  if (shape) {
+    hipLaunchKernelGGL(zmpc_push_state_shape_kernel,
+                       dim3((unsigned)((n + kShapeThreads - 1) / kShapeThreads)),
+                       dim3(kShapeThreads), 0, s, n, ws, w.w, (int64_t)w.dur, ws + 2 * n);
+    S = ws + 2 * n;
+  }
+  // workgroups per walk: one per 1024 pairs, fewer where the grid would pass 2^31 − 1 blocks
+  int64_t chunks = (3 * n + 4 * kAddThreads - 1) / (4 * kAddThreads);
+  if (chunks > 0x7fffffff / B) chunks = 0x7fffffff / B;
+  if (chunks < 1) chunks = 1;
+  hipLaunchKernelGGL(zmpc_push_add_kernel, dim3((unsigned)(B * chunks)), dim3(kAddThreads), 0, s, n,
+                     (int)chunks, w.amp, w.cols, w.col[0], w.col[1], w.steps, w.step, S, c.hist);
   e = hipGetLastError();
   const hipError_t ef = hipFreeAsync(ws, s);
   return e != hipSuccess ? e : ef;

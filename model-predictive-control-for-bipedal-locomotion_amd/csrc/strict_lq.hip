@@ -132,6 +132,7 @@ struct LqArgs {
   int64_t nblocks;       // blocks of the whole launch (G waves each)
   unsigned long long* prof;  // diagnostics build only (ZMPC_LQ_PROF): clocks per phase and axis
   int skip_axis;         // diagnostics build only (ZMPC_LQ_SKIP): 1 / 2 = the x / y tasks end at once
+  PushArgs push;         // the push window of zmpc_rollout_pushed; all zero: the kick above
 };
 
 // Slot q's flag in a segment's word: its 2-bit field, sign-extended.
@@ -682,7 +683,10 @@ __device__ __forceinline__ void ck_load_s(const CkIO<NT>& io, const double* ck, 
 // the loop, the loop's live ranges cost the sweeps ≈75 more spilled registers (config 4 76.2
 // ms, config 3 65.7); as a lambda the queue form spills 37–60 and runs config 4 in 72.3 ms,
 // at +1 % for config 3 (profiles/r4/r4z/, r4aa/).
-template <int S, int G, bool NT, bool RUNS, bool QUEUE>
+// PUSH: the instances of zmpc_rollout_pushed, whose time loop takes a push window (a.push) on
+// either axis; the others take the one-sample y kick as before, instruction for instruction (the
+// window in the kick's instances cost config 3 1.2 %).
+template <int S, int G, bool NT, bool RUNS, bool QUEUE, bool PUSH = false>
 __global__ void __launch_bounds__(64 * G, 2)
     zmpc_strict_lq_kernel(LqArgs a, const double* __restrict__ tab) {
   extern __shared__ __attribute__((aligned(16))) unsigned char lq_smem[];
@@ -797,10 +801,17 @@ __global__ void __launch_bounds__(64 * G, 2)
     xpark[128 + lane] = x[2];
   }
   int fq = 0;
-  const int kstep =
-      (!a.window_mode && axis == 1 && a.kick != nullptr && valid)
-          ? (int)(a.kick_steps ? a.kick_steps[b] : a.kick_step)
-          : -1;
+  // PUSH: the lane's push window, steps [kstep, kstep + pdur) (zmpc.h "The push, stated once")
+  int kstep;
+  if constexpr (PUSH)
+    kstep = (!a.window_mode && valid && push_amp(a.push, a.kick, b, axis) != nullptr)
+                ? push_start(a.push, a.kick_steps, a.kick_step, b, a.n)
+                : kNoPush;
+  else
+    kstep = (!a.window_mode && axis == 1 && a.kick != nullptr && valid)
+                ? (int)(a.kick_steps ? a.kick_steps[b] : a.kick_step)
+                : -1;
+  const unsigned pdur = PUSH ? push_dur(a.push) : 1u;
 
   // Each lane walks its own timestep i: a pass runs for every lane still inside its rollout
   // and at most LQ_DRIFT timesteps ahead of the wave's slowest lane (so a slot's bound loads
@@ -1012,7 +1023,13 @@ __global__ void __launch_bounds__(64 * G, 2)
         xn[0] = x0 + a.T * x1 + a.T2 * x2 + a.T3 * u0;
         xn[1] = x1 + a.T * x2 + a.T2 * u0;
         xn[2] = x2 + a.T * u0;
-        if ((int)i == kstep) xn[1] -= a.kick[b];  // force kick (zmp_controller.py:90,105-106)
+        // force kick (zmp_controller.py:90,105-106); PUSH: over the window's steps
+        if constexpr (PUSH) {
+          if ((unsigned)(i - kstep) < pdur)
+            xn[1] -= push_value(a.push, push_amp(a.push, a.kick, b, axis), (unsigned)(i - kstep));
+        } else {
+          if ((int)i == kstep) xn[1] -= a.kick[b];
+        }
         if (!(isfinite(xn[0]) && isfinite(xn[1]) && isfinite(xn[2]))) fq |= ZMPC_ST_NONFINITE;
         xpark[lane] = xn[0];
         xpark[64 + lane] = xn[1];
@@ -1252,21 +1269,31 @@ struct LqVariant {
   void (*q_kernel_nt)(LqArgs, const double*);
   void (*q_kernel_runs)(LqArgs, const double*);
   void (*q_kernel_runs_nt)(LqArgs, const double*);
+  // the push-window instances (zmpc_rollout_pushed), cached checkpoints: bounds by rows, by runs,
+  // and by runs with the task queue (G = 8 only; null otherwise)
+  void (*p_kernel)(LqArgs, const double*);
+  void (*p_kernel_runs)(LqArgs, const double*);
+  void (*p_q_kernel_runs)(LqArgs, const double*);
 };
 
 #define ZMPC_LQK(G, Q)                                                               \
   zmpc_strict_lq_kernel<LQ_S, G, false, false, Q>, zmpc_strict_lq_kernel<LQ_S, G, true, false, Q>, \
       zmpc_strict_lq_kernel<LQ_S, G, false, true, Q>, zmpc_strict_lq_kernel<LQ_S, G, true, true, Q>
-#define ZMPC_LQV(G) {G, ZMPC_LQK(G, false), nullptr, nullptr, nullptr, nullptr}
+#define ZMPC_LQP(G) \
+  zmpc_strict_lq_kernel<LQ_S, G, false, false, false, true>, \
+      zmpc_strict_lq_kernel<LQ_S, G, false, true, false, true>
+#define ZMPC_LQV(G) {G, ZMPC_LQK(G, false), nullptr, nullptr, nullptr, nullptr, ZMPC_LQP(G), nullptr}
 // (The queue form exists for run-length bounds only: with the bounds staged one row per sample,
 // ZMPC_OPT_STRICT_BOUNDS = 1, its instances spill 20 B — those launches take the one-round form.)
 const LqVariant kLqVariants[] = {
     {8, ZMPC_LQK(8, false), nullptr, nullptr, zmpc_strict_lq_kernel<LQ_S, 8, false, true, true>,
-     zmpc_strict_lq_kernel<LQ_S, 8, true, true, true>},  // default
+     zmpc_strict_lq_kernel<LQ_S, 8, true, true, true>, ZMPC_LQP(8),
+     zmpc_strict_lq_kernel<LQ_S, 8, false, true, true, true>},  // default
     ZMPC_LQV(4),  // N up to 2176 (the default G = 8: up to 896)
     ZMPC_LQV(2),  // N up to 2464 (ZMPC_STRICT_MAX_N)
 };
 #undef ZMPC_LQV
+#undef ZMPC_LQP
 #undef ZMPC_LQK
 
 // The kernels of a workgroup shape (dispatch.h lq_shape: G = 8, 4 or 2).
@@ -1309,6 +1336,10 @@ hipError_t launch_lq(const zmpc_plan* p, LqArgs& a, int64_t waves, hipStream_t s
   auto k = a.rs ? (nt ? var->kernel_runs_nt : var->kernel_runs) : (nt ? var->kernel_nt : var->kernel);
   auto kq = a.rs ? (nt ? var->q_kernel_runs_nt : var->q_kernel_runs)
                  : (nt ? var->q_kernel_nt : var->q_kernel);
+  if (a.push.amp != nullptr) {  // a push window: its own instances
+    k = a.rs ? var->p_kernel_runs : var->p_kernel;
+    kq = a.rs ? var->p_q_kernel_runs : nullptr;
+  }
   // more blocks than the chip holds at once: a grid of the resident blocks and a task queue
   // (an x wave is done long before its SIMD's y wave; with one task per wave its slot idles
   // until the whole block has finished, while a queue refills it with the next y wave)
@@ -1376,7 +1407,8 @@ hipError_t zmpc_strict_lq_set_attrs() {
   hipError_t e = hipSuccess;
   for (const LqVariant& c : kLqVariants)
     for (auto k : {c.kernel, c.kernel_nt, c.kernel_runs, c.kernel_runs_nt, c.q_kernel,
-                   c.q_kernel_nt, c.q_kernel_runs, c.q_kernel_runs_nt})
+                   c.q_kernel_nt, c.q_kernel_runs, c.q_kernel_runs_nt, c.p_kernel, c.p_kernel_runs,
+                   c.p_q_kernel_runs})
       if (k != nullptr && e == hipSuccess)
         e = hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize,
                                 160 * 1024);
@@ -1410,6 +1442,7 @@ hipError_t zmpc_launch_rollout_strict_lq(const zmpc_plan* p, const RolloutCall& 
   a.kick = c.kick;
   a.kick_step = c.kick_step;
   a.kick_steps = c.kick_steps;
+  a.push = c.push;
   a.out = c.hist;
   a.status = c.status;
   hipError_t e = hipSuccess;
@@ -1437,7 +1470,8 @@ hipError_t zmpc_launch_rollout_strict_lq(const zmpc_plan* p, const RolloutCall& 
                                  : (size_t)2 * a.groups * a.rows * 64 * 2;
   // kick order (order.hip): walks with per-walk kicks sorted by (kick step, kick) onto lanes,
   // when there is more than one wave of them (ZMPC_OPT_KICK_ORDER = 0 keeps the input order)
-  const bool ordered = p->opt[ZMPC_OPT_KICK_ORDER] != 0 && c.kick != nullptr && B > 64;
+  const bool ordered =
+      p->opt[ZMPC_OPT_KICK_ORDER] != 0 && (c.kick != nullptr || c.push.amp != nullptr) && B > 64;
   const size_t perm_doubles = ordered ? ((size_t)B * 4 + 7) / 8 : 0;
   const size_t ord_doubles = ordered ? (zmpc_kick_order_bytes(B) + 7) / 8 : 0;
   double* ws = nullptr;
@@ -1453,7 +1487,7 @@ hipError_t zmpc_launch_rollout_strict_lq(const zmpc_plan* p, const RolloutCall& 
   a.perm = nullptr;
   if (ordered) {
     int32_t* perm = reinterpret_cast<int32_t*>(ws + ck_doubles + st_doubles);
-    e = zmpc_kick_order(c.kick, c.kick_steps, c.kick_step, B, perm,
+    e = zmpc_kick_order(c.kick, c.kick_steps, c.kick_step, c.push, B, perm,
                         ws + ck_doubles + st_doubles + perm_doubles, s);
     a.perm = perm;
   }

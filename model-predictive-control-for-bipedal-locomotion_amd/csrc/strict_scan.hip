@@ -65,6 +65,7 @@ struct ScanArgs {
   // z-form step constants (strict_eta.h fill_eta)
   double pi, ipi, ipi2, gp, rho, eps, epsg, epsg2, quz0, epi, tolnu;
   double iR, piR, rhoR, rhoP2;  // slot elements: 1/R, π/R, ρ/R, ρ/π² (R = π² + ρ)
+  PushArgs push;  // the push window of zmpc_rollout_pushed; all zero: the kick above
 };
 
 // symmetric 3×3 in 6 doubles: 00 01 02 11 12 22
@@ -377,10 +378,11 @@ __global__ void __launch_bounds__(64, (C >= ZMPC_SCAN_ONE_WAVE_C ? 1 : 2))
       h[2] = x[2];
     }
   }
-  const int64_t kstep = (!a.window_mode && axis == 1 && a.kick != nullptr)
-                            ? (a.kick_steps ? a.kick_steps[b] : a.kick_step)
-                            : -1;
-  const double kv = (kstep >= 0) ? a.kick[b] : 0.0;
+  // the instance's push window: steps [kstep, kstep + pdur) (zmpc.h "The push, stated once";
+  // the legacy kick is the window of one step on y)
+  const double* const pamp = a.window_mode ? nullptr : push_amp(a.push, a.kick, b, axis);
+  const int kstep = pamp ? push_start(a.push, a.kick_steps, a.kick_step, b, a.n) : kNoPush;
+  const unsigned pdur = push_dur(a.push);
   int f[C];  // working-set flags of the lane's slots: 0 free, +1 at z_max, −1 at z_min
 #pragma unroll
   for (int q = 0; q < C; ++q) f[q] = 0;
@@ -629,7 +631,9 @@ __global__ void __launch_bounds__(64, (C >= ZMPC_SCAN_ONE_WAVE_C ? 1 : 2))
     xn[0] = x[0] + a.T * x[1] + a.T2 * x[2] + a.T3 * u0;
     xn[1] = x[1] + a.T * x[2] + a.T2 * u0;
     xn[2] = x[2] + a.T * u0;
-    if (i == kstep) xn[1] -= kv;  // force kick (zmp_controller.py:90,105-106)
+    // force kick (zmp_controller.py:90,105-106), over the window's steps
+    if ((unsigned)((int)i - kstep) < pdur)
+      xn[1] -= push_value(a.push, pamp, (unsigned)((int)i - kstep));
     if (!(isfinite(xn[0]) && isfinite(xn[1]) && isfinite(xn[2]))) fq |= ZMPC_ST_NONFINITE;
     x[0] = xn[0];
     x[1] = xn[1];
@@ -762,6 +766,7 @@ hipError_t zmpc_launch_rollout_strict_scan(const zmpc_plan* p, const RolloutCall
   a.kick = c.kick;
   a.kick_step = c.kick_step;
   a.kick_steps = c.kick_steps;
+  a.push = c.push;
   a.out = c.hist;
   a.status = c.status;
   return launch(p, a, s);

@@ -78,8 +78,53 @@ __host__ __device__ constexpr int kffa_rows(int N) { return (N + 2) / 2 + 8; }
 // (ksum_rows / ksum_s0, the layout of the suffix sums of k, and the FFT table sizes kFftPT,
 // kFftPmin, kFftGComplex are in dispatch.h: they enter the LDS budgets of the launch rules)
 
-// The arguments of one zmpc_rollout / zmpc_rollout_kicks call (include/zmpc.h), filled once in
-// capi.hip and handed down by reference.
+// The push window of a pushed rollout (include/zmpc.h, "The push, stated once") as the strict and
+// Herdt kernels take it, by value inside their argument structs.  All zero means the legacy
+// one-sample y kick of the struct's own kick fields, so a zero-initialised argument struct filled
+// by name behaves as before.
+struct PushArgs {
+  const double* amp;     // [B, cols] device, or null: the legacy kick
+  const double* w;       // [dur] device profile, or null: ones (no product)
+  const int64_t* steps;  // [B] start steps, or null: step
+  int64_t step;
+  int dur;     // D, clamped to n by the launcher (a push past the walk's end is truncated anyway)
+  int cols;    // C, the columns of amp
+  int col[2];  // the column of axis a (0: x, 1: y) in amp, −1: the axis is not pushed
+};
+
+// "no push" as a start step: (unsigned)(i − kNoPush) >= 2^31 for every timestep 0 <= i < 2^24
+constexpr int kNoPush = 0x7fffffff;
+
+// Where the amplitude of (walk b, axis) is read, null when the axis takes no push: amp[b, col] of
+// a push window, kick[b] on the y axis otherwise.
+__host__ __device__ inline const double* push_amp(const PushArgs& p, const double* kick,
+                                                  int64_t b, int axis) {
+  if (p.amp) return p.col[axis] >= 0 ? p.amp + b * p.cols + p.col[axis] : nullptr;
+  return (kick && axis == 1) ? kick + b : nullptr;
+}
+
+// The start step of walk b's push in a walk of n samples, kNoPush outside [0, n − 1).
+__host__ __device__ inline int push_start(const PushArgs& p, const int64_t* kick_steps,
+                                          int64_t kick_step, int64_t b, int64_t n) {
+  const int64_t s = p.amp ? (p.steps ? p.steps[b] : p.step)
+                          : (kick_steps ? kick_steps[b] : kick_step);
+  return (s >= 0 && s < n - 1) ? (int)s : kNoPush;
+}
+
+// The window's length as the range test (unsigned)(i − start) < D takes it
+__host__ __device__ inline unsigned push_dur(const PushArgs& p) {
+  return p.amp ? (unsigned)p.dur : 1u;
+}
+
+// What sample i + 1's velocity is lowered by at j = i − start, read at the point of use: the
+// amplitude itself without a profile, so that D = 1 is the legacy kick's arithmetic.
+__host__ __device__ inline double push_value(const PushArgs& p, const double* ap, unsigned j) {
+  const double am = *ap;
+  return p.w ? am * p.w[j] : am;
+}
+
+// The arguments of one zmpc_rollout / zmpc_rollout_kicks / zmpc_rollout_pushed call
+// (include/zmpc.h), filled once in capi.hip and handed down by reference.
 struct RolloutCall {
   int64_t B, n;
   const double *zmax, *zmin;
@@ -89,6 +134,7 @@ struct RolloutCall {
   const int64_t* kick_steps;  // per-walk kick steps, or null: kick_step
   double* hist;
   int32_t* status;  // may be null
+  PushArgs push;    // zmpc_rollout_pushed: the window (kick is null then); all zero otherwise
 };
 
 // The arguments of one zmpc_step call.
@@ -141,6 +187,11 @@ struct PushCall {
 // otherwise) could not be allocated
 hipError_t zmpc_launch_push_map(const zmpc_plan* p, const PushCall& c, hipStream_t s);
 hipError_t zmpc_push_map_set_attrs();
+
+// the state response of a push window added to an unpushed history of a non-strict plan
+// (pushmap.hip): hist[b, s_b + d, a, :] −= amp[b, a]·Σ_j w_j·Ā^(d−j−1)·e1 on the axes of c.push.
+// hipErrorOutOfMemory: the stream-ordered workspace (4n doubles, 8n with a profile or D > 1)
+hipError_t zmpc_launch_push_response(const zmpc_plan* p, const RolloutCall& c, hipStream_t s);
 
 // unconstrained rollout / step (rollout.hip)
 hipError_t zmpc_launch_rollout_unc(const zmpc_plan* p, const RolloutCall& c, hipStream_t s,
@@ -195,11 +246,13 @@ hipError_t zmpc_launch_step_strict_scan(const zmpc_plan* p, const StepCall& c, h
 bool zmpc_strict_scan_supported(const zmpc_plan* p);
 
 // walk order for the lane-per-instance kernels (order.hip): perm[B] = the walks sorted by
-// (kick step, kick), so that a wave's lanes take similar disturbances; ws of
-// zmpc_kick_order_bytes(B) bytes (device, stream-ordered)
+// (kick step, kick) — of a push window (push.amp set) by (start step, the larger |amp| of its
+// axes) — so that a wave's lanes take similar disturbances; ws of zmpc_kick_order_bytes(B) bytes
+// (device, stream-ordered)
 size_t zmpc_kick_order_bytes(int64_t B);
 hipError_t zmpc_kick_order(const double* kick, const int64_t* kick_steps, int64_t kick_step,
-                           int64_t B, int32_t* perm, void* ws, hipStream_t s);
+                           const PushArgs& push, int64_t B, int32_t* perm, void* ws,
+                           hipStream_t s);
 
 // Herdt joint footstep QP (herdt.hip); support states as cop_generator.State
 constexpr int ZMPC_STANDING = 0, ZMPC_DOUBLE_SUPPORT = 1, ZMPC_SINGLE_SUPPORT = 2;
@@ -207,9 +260,9 @@ hipError_t zmpc_launch_herdt(const zmpc_plan* p, const zmpc_herdt_params* prm, i
                              int64_t n, int window_mode, const double* vref, int64_t vs,
                              const int8_t* st, int64_t ss, const int32_t* nb, int64_t ns,
                              const double* x0, const double* kick, int64_t kick_step,
-                             const int8_t* cur0, const double* fc0, const int8_t* side0,
-                             double* hist, double* foot, int32_t* status, hipStream_t s,
-                             std::string* why);
+                             const PushArgs& push, const int8_t* cur0, const double* fc0,
+                             const int8_t* side0, double* hist, double* foot, int32_t* status,
+                             hipStream_t s, std::string* why);
 hipError_t zmpc_herdt_set_attrs();
 
 hipError_t zmpc_rollout_unc_set_attrs();

@@ -83,6 +83,11 @@ SIGNATURES = {
                                           _c_dbl_p, _c_dbl_p, ctypes.c_int64, _c_dbl_p, _c_dbl_p,
                                           ctypes.c_void_p, _c_dbl_p, ctypes.c_void_p,
                                           ctypes.c_void_p]),
+    # ... x0, push (const zmpc_push*, a ZmpcPush passed byref), hist, status, stream
+    "zmpc_rollout_pushed": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64,
+                                           _c_dbl_p, _c_dbl_p, ctypes.c_int64, _c_dbl_p,
+                                           ctypes.c_void_p, _c_dbl_p, ctypes.c_void_p,
+                                           ctypes.c_void_p]),
     "zmpc_walk_metrics": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64,
                                          _c_dbl_p, _c_dbl_p, _c_dbl_p, ctypes.c_int64,
                                          ctypes.c_void_p, _c_dbl_p, ctypes.c_void_p]),
@@ -110,11 +115,27 @@ SIGNATURES = {
                                           ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p,
                                           ctypes.c_int64, _c_dbl_p, _c_dbl_p, ctypes.c_int64,
                                           _c_dbl_p, _c_dbl_p, ctypes.c_void_p, ctypes.c_void_p]),
+    # ... x0, push (const zmpc_push*), hist, foot, status, stream
+    "zmpc_herdt_rollout_pushed": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64,
+                                                 ctypes.c_int64, _c_dbl_p, ctypes.c_int64,
+                                                 ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p,
+                                                 ctypes.c_int64, _c_dbl_p, ctypes.c_void_p,
+                                                 _c_dbl_p, _c_dbl_p, ctypes.c_void_p,
+                                                 ctypes.c_void_p]),
     "zmpc_herdt_step": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64,
                                        _c_dbl_p, _c_dbl_p, ctypes.c_void_p, ctypes.c_void_p,
                                        _c_dbl_p, ctypes.c_void_p, _c_dbl_p, _c_dbl_p,
                                        ctypes.c_void_p, ctypes.c_void_p]),
 }
+
+
+class ZmpcPush(ctypes.Structure):
+    """include/zmpc.h zmpc_push: the push window of zmpc_rollout_pushed and
+    zmpc_herdt_rollout_pushed (device pointers as integers)."""
+    _fields_ = [("amp", ctypes.c_void_p), ("axes", ctypes.c_int32), ("steps", ctypes.c_void_p),
+                ("step", ctypes.c_int64), ("profile", ctypes.c_void_p),
+                ("duration", ctypes.c_int64)]
+
 
 _lib = None
 _lock = threading.Lock()

@@ -19,6 +19,10 @@ A push that lasts several samples, with or without a force profile, has the resp
 ``zmpc_push_map_shaped`` (``csrc/pushmap.hip``) evaluates that on either axis or both,
 ``push_map_shaped_reference`` is its checker, and ``PushMap.weakest_push`` and ``PushMap.rose``
 (``planar_push``) read the columns (+x, −x, +y, −y), the latter along any planar direction.
+
+``Push`` describes the shove itself — force, direction, start step, duration, profile — for the
+pushed rollouts of every controller (``zmpc_rollout_pushed``, ``zmpc_herdt_rollout_pushed``;
+``Plan.rollout(push=)``, the batch methods of ``ZMPController``).
 """
 
 import numpy as np
@@ -338,6 +342,89 @@ def unit_directions(directions):
     if (norm == 0).any():
         raise ValueError("a direction must not be the zero vector")
     return d / norm[..., None]
+
+
+class Push:
+    """A shove for a rollout (include/zmpc.h zmpc_push, "The push, stated once"): `force` newtons
+    along `direction`, from history step `step` on, for `duration` samples with force
+    F·profile[j] in its j-th sample.
+
+    force      scalar or [B], in newtons
+    direction  a sign (scalar): ±F on the y axis, as the reference pushes
+               (zmp_controller.py:105-106); or a planar vector (dx, dy), or [B, 2] of them,
+               normalised by unit_directions.  A component that is exactly zero in every
+               direction leaves its axis out: (0, −1) is a y push, (1, 0) an x push
+    step       an int, or [B] start steps (a step outside [0, n − 1): no push for that walk)
+    duration   D >= 1, in samples;  profile  None (constant) or D finite weights (check_profile)
+
+    +F on an axis lowers that axis' velocity.  ``axes`` is "x", "y" or "xy";
+    ``amplitudes(dt, m, B)`` the [B, C] velocity steps dt·F·dir/m the kernels take."""
+
+    __slots__ = ("force", "direction", "step", "duration", "profile", "axes")
+
+    def __init__(self, force, direction, step, duration=1, profile=None):
+        F = np.asarray(force, np.float64)
+        if F.ndim > 1 or not np.isfinite(F).all():
+            raise ValueError(f"force must be a finite scalar or [B], got shape {tuple(F.shape)}")
+        d = np.asarray(direction, np.float64)
+        if d.ndim == 0:
+            if not np.isfinite(d) or d == 0:
+                raise ValueError("a sign direction must be finite and non-zero")
+            unit, axes = np.array([[0.0, float(np.sign(d))]]), "y"
+        else:
+            unit = unit_directions(d)
+            if unit.ndim > 2:
+                raise ValueError(f"direction must be a sign, (dx, dy) or [B, 2], got shape "
+                                 f"{tuple(d.shape)}")
+            unit = unit.reshape(-1, 2)
+            axes = "y" if (unit[:, 0] == 0).all() else "x" if (unit[:, 1] == 0).all() else "xy"
+        st = np.asarray(step)
+        if st.ndim > 1 or st.dtype.kind not in "iu":
+            raise ValueError("step must be an integer or a [B] integer array")
+        self.duration, self.profile = check_profile(duration, profile)
+        self.force, self.direction, self.axes = F, unit, axes
+        self.step = int(st) if st.ndim == 0 else st.astype(np.int64)
+
+    def __repr__(self):
+        return (f"Push(axes={self.axes!r}, step={self.step!r}, duration={self.duration}"
+                f"{'' if self.profile is None else ', shaped'})")
+
+    def batch(self):
+        """The batch size the push asks for (None: it fits any)."""
+        sizes = {int(a.shape[0]) for a in (self.force, self.direction[:, 0],
+                                          np.asarray(self.step)) if a.ndim == 1 and a.shape[0] != 1}
+        if len(sizes) > 1:
+            raise ValueError(f"force, direction and step disagree on the batch size: {sorted(sizes)}")
+        return sizes.pop() if sizes else None
+
+    def amplitudes(self, dt, m, B):
+        """amp [B, C] = dt·F_b·dir_(b, a)/m in m/s, C columns in the order of ``axes``."""
+        nb = self.batch()
+        if nb is not None and nb != B:
+            raise ValueError(f"the push is for {nb} walks, the batch holds {B}")
+        F = np.broadcast_to(self.force.reshape(-1), (B,))
+        unit = np.broadcast_to(self.direction, (B, 2))
+        cols = [a for a in (0, 1) if AXES[self.axes] >> a & 1]
+        return np.ascontiguousarray(dt * (F[:, None] * unit[:, cols]) / m)
+
+    def velocity_steps(self, dt, m, B, n):
+        """dvel [B, n, 2]: what the velocity of sample i + 1 is lowered by at history step i, on
+        (x, y) — the statement of include/zmpc.h in NumPy, for the checkers."""
+        amp = self.amplitudes(dt, m, B)
+        cols = [a for a in (0, 1) if AXES[self.axes] >> a & 1]
+        steps = np.broadcast_to(np.asarray(self.step, np.int64).reshape(-1), (B,))
+        dvel = np.zeros((B, n, 2))
+        for b in range(B):
+            s = int(steps[b])
+            if not 0 <= s < n - 1:
+                continue
+            for j in range(self.duration):
+                if s + j >= n - 1:
+                    break
+                for c, a in enumerate(cols):
+                    dvel[b, s + j, a] = amp[b, c] if self.profile is None \
+                        else amp[b, c] * self.profile[j]
+        return dvel
 
 
 class PushMap:

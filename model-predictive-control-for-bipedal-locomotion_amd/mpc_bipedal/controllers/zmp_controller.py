@@ -16,7 +16,9 @@ disturbance scenarios at once, taking and returning torch device tensors; ``walk
 the ZMP stay inside the support box, per walk, reduced on the device), ``critical_force``
 (the largest push each scenario survives, by bisection over batched rollouts), and for the
 unconstrained controller ``push_map`` / ``critical_force_exact`` (that push in closed form, at
-every step and in both directions, from one unpushed rollout).
+every step and in both directions, from one unpushed rollout).  The batch methods and
+``critical_force`` also take a shove of any length, shape and planar direction
+(``push=analysis.Push(...)``; ``duration=``, ``profile=``) on every controller.
 """
 
 import warnings
@@ -25,7 +27,8 @@ from typing import Optional, Tuple
 import numpy as np
 import torch
 
-from ..analysis import NMETRICS, PushMap, WalkMetrics, planar_push, unit_directions
+from ..analysis import (NMETRICS, Push, PushMap, WalkMetrics, check_profile, planar_push,
+                        unit_directions)
 from ..config import MPCConfig
 from ..models.lipm_model import lipm_matrices
 from ..solver import get_plan
@@ -198,12 +201,15 @@ class ZMPController:
         return xn[0].reshape(3, 1), xn[1].reshape(3, 1), fx, fy
 
     def generate_com_trajectory_herdt_batch(self, x_init, v_ref, state_ref, F_ext=None,
-                                            return_status: bool = False):
+                                            return_status: bool = False, push: Push = None):
         """Many Herdt walks at once (addition): x_init [B,2,3] or None; v_ref [B,n,2] or a
         shared [n,2]; state_ref [B,n] or a shared [n] (State enums or int8 codes); F_ext [B]
         or None.  Returns (com [B,n,2], hist [B,n,2,3], foot [B,n,2]) on the device; with
         return_status=True also the per-walk status [B] (ZMPC_ST_* flags) instead of raising
-        or warning on a failed walk."""
+        or warning on a failed walk.  push: an analysis.Push — a shove of any length, shape and
+        direction instead of F_ext (zmpc_herdt_rollout_pushed; not together with F_ext)."""
+        if push is not None and F_ext is not None:
+            raise ValueError("give either F_ext or push, not both")
         v = torch.as_tensor(v_ref, dtype=torch.float64)
         n = int(v.shape[-2])
         st = herdt.encode_states(state_ref) if not isinstance(state_ref, torch.Tensor) \
@@ -214,6 +220,8 @@ class ZMPController:
             B = int(v.shape[0])
         elif st.ndim == 2:
             B = int(st.shape[0])
+        elif push is not None:
+            B = push.batch() or 1
         else:
             B = 1 if F_ext is None else int(np.size(F_ext))
         x0 = np.zeros((B, 2, 3)) if x_init is None else x_init
@@ -221,12 +229,12 @@ class ZMPController:
         if F_ext is not None:
             kick = self.config.dt * np.asarray(F_ext, np.float64).reshape(B) / self.config.m
         hist, foot, status = self._herdt_rollout(x0, v_ref, st, kick, n // 2,
-                                                 check=not return_status)
+                                                 check=not return_status, push=push)
         if return_status:
             return hist[..., 0], hist, foot, status
         return hist[..., 0], hist, foot
 
-    def _herdt_rollout(self, x0, v_ref, st, kick, kick_step, check=True):
+    def _herdt_rollout(self, x0, v_ref, st, kick, kick_step, check=True, push=None):
         plan = self._plan()
         N = plan.N
         st2 = np.atleast_2d(st)
@@ -236,15 +244,20 @@ class ZMPController:
         nb = np.array([[t[0] for t in herdt.find_nb_steps(p)][:n] for p in pad], np.int32)
         if st.ndim == 1:
             nb = nb[0]
-        hist, foot, status = plan.herdt_rollout(prm, v_ref, st, nb, x0, kick=kick,
-                                                kick_step=kick_step)
+        if push is not None:
+            hist, foot, status = plan.herdt_rollout(prm, v_ref, st, nb, x0, push=push,
+                                                    mass=self.config.m)
+        else:
+            hist, foot, status = plan.herdt_rollout(prm, v_ref, st, nb, x0, kick=kick,
+                                                    kick_step=kick_step)
         if check:
             self._herdt_status(status)
         return hist, foot, status
 
     # ------------------------------------------------------------------ batched additions
     def generate_state_trajectory_batch(self, x_init, z_max, z_min, F_ext=None,
-                                        force_step: Optional[int] = None, walk_lengths=None):
+                                        force_step: Optional[int] = None, walk_lengths=None,
+                                        push: Push = None):
         """Many walks at once; every input may be NumPy or a torch tensor.
 
         x_init : [B,2,3] initial (x-axis, y-axis) states, or None for zeros
@@ -255,11 +268,25 @@ class ZMPController:
         walk_lengths : [B] sample counts of ragged walks padded to n with their last row
                 (CoPGenerator.generate_cop_batch); the force then hits step n_b//2 of each
                 walk and hist[b, :n_b] is walk b's history
+        push : an analysis.Push — a shove of any length, shape and direction instead of F_ext
+                (zmpc_rollout_pushed).  It carries its own start step(s): together with F_ext,
+                force_step or walk_lengths it raises ValueError (hist[b, :n_b] of a ragged walk
+                is still walk b's history; give the steps n_b // 2 in the push)
         Returns (hist [B,n,2,3], status [B]) on the plan's device.
         """
+        if push is not None and F_ext is not None:
+            raise ValueError("give either F_ext or push, not both")
+        if push is not None and (force_step is not None or walk_lengths is not None):
+            raise ValueError("a push carries its own start step(s): force_step and walk_lengths "
+                             "belong to F_ext")
         plan, zmax_t, x0, kick, step = self._batch_inputs(x_init, z_max, F_ext, force_step,
                                                           walk_lengths)
-        hist, st = plan.rollout(zmax_t, z_min, x0, kick=kick, kick_step=step)
+        if push is not None:
+            if x_init is None and zmax_t.dim() == 2 and push.batch():
+                x0 = x0.expand(push.batch(), 2, 3).contiguous()
+            hist, st = plan.rollout(zmax_t, z_min, x0, push=push, mass=self.config.m)
+        else:
+            hist, st = plan.rollout(zmax_t, z_min, x0, kick=kick, kick_step=step)
         if plan.strict:
             self._raise_on_status(st)
         return hist, st
@@ -303,10 +330,12 @@ class ZMPController:
         return WalkMetrics(m), st
 
     def generate_com_trajectory_batch(self, x_init, z_max, z_min, F_ext=None,
-                                      force_step: Optional[int] = None, walk_lengths=None):
-        """Batched generate_com_trajectory_wieber: (com [B,n,2], hist [B,n,2,3]) on device."""
+                                      force_step: Optional[int] = None, walk_lengths=None,
+                                      push: Push = None):
+        """Batched generate_com_trajectory_wieber: (com [B,n,2], hist [B,n,2,3]) on device;
+        push as generate_state_trajectory_batch."""
         hist, _ = self.generate_state_trajectory_batch(x_init, z_max, z_min, F_ext, force_step,
-                                                       walk_lengths)
+                                                       walk_lengths, push=push)
         return hist[..., 0], hist
 
     def zmp(self, hist):
@@ -335,7 +364,7 @@ class ZMPController:
                        F_hi: float = 1000.0, iters: int = 30, max_violation: float = 1e-9,
                        max_com_dev: Optional[float] = None,
                        max_dcm_end: Optional[float] = None, walk_lengths=None,
-                       fused: bool = False):
+                       fused: bool = False, duration: int = 1, profile=None):
         """Largest push each scenario survives (addition): the question the F_ext sweep of
         run_compare_resistance.py:87-169 puts to the eye, answered by bisection on the device.
 
@@ -362,15 +391,33 @@ class ZMPController:
         with a passing unpushed walk that is exact: the closed loop is linear, every ZMP sample
         is affine in F, so the passing set is an interval that contains 0.  For strict plans
         it is an assumption (the clamped ZMP hides the push until the QP fails or the CoM
-        criteria trip)."""
+        criteria trip).
+
+        duration, profile: a shove that lasts `duration` samples from force_step on, with force
+        F·profile[j] in its j-th sample (None: constant).  direction may also hold planar vectors
+        (dx, dy), as a two-dimensional [1, 2] or [B, 2] array (a bare pair stays two signs, as in
+        critical_force_exact): F is then the magnitude of a push along that direction.  A scalar
+        or [B] sign with duration 1 and no profile keeps the launches above; otherwise each
+        evaluation is one pushed rollout (zmpc_rollout_pushed — on a strict plan the push window
+        of the strict kernels) plus walk_metrics, and fused=True raises ValueError."""
+        D, w = check_profile(duration, profile)
+        planar = np.ndim(direction) == 2
+        shove = planar or D != 1 or w is not None
+        if shove and fused:
+            raise ValueError("fused=True has no pushed form: a shove (duration, profile or a "
+                             "planar direction) runs a pushed rollout plus walk_metrics")
+        unit = unit_directions(direction) if planar else None
         plan = self._plan()
         dev = torch.device("cuda", plan.device)
         f64 = dict(dtype=torch.float64, device=dev)
         zmax_t = torch.as_tensor(z_max, **f64).contiguous()
         zmin_t = torch.as_tensor(z_min, **f64).contiguous()
         n = int(zmax_t.shape[-2])
-        sizes = [int(np.shape(a)[0]) for a in (force_step, direction, walk_lengths)
+        sizes = [int(np.shape(a)[0]) for a in (force_step, walk_lengths) + (() if planar else
+                                                                            (direction,))
                  if a is not None and np.ndim(a) == 1]
+        if planar and unit.shape[0] > 1:  # K > 1 planar directions: one scenario each
+            sizes.append(int(unit.shape[0]))
         if x_init is not None:
             x0 = torch.as_tensor(x_init, **f64)
             B = int(x0.shape[0])
@@ -379,10 +426,13 @@ class ZMPController:
             x0 = torch.zeros((B, 2, 3), **f64)
         if any(s != B for s in sizes):
             raise ValueError("force_step, direction and walk_lengths must be scalars or "
-                             f"[B] = [{B}]")
+                             f"[B] = [{B}] (planar directions [1, 2] or [B, 2])")
         if not (F_hi > 0) or iters < 0:
             raise ValueError("need F_hi > 0 and iters >= 0")
-        sign = torch.sign(torch.as_tensor(direction, **f64)).expand(B).contiguous()
+        if planar:
+            sign = None
+        else:
+            sign = torch.sign(torch.as_tensor(direction, **f64)).expand(B).contiguous()
         lengths = None
         if walk_lengths is not None:
             lengths = torch.as_tensor(walk_lengths, dtype=torch.int64, device=dev).reshape(B)
@@ -394,7 +444,19 @@ class ZMPController:
             step = torch.as_tensor(force_step, dtype=torch.int64, device=dev)
         kick = torch.zeros(B, **f64)
         metrics = torch.empty((B, NMETRICS), **f64)
-        if fused:
+        if shove:
+            # one newton along each scenario's direction; the bisection scales the amplitudes
+            if planar:
+                d1 = np.broadcast_to(unit, (B, 2))
+            else:
+                d1 = np.stack([np.zeros(B), sign.cpu().numpy()], axis=1)
+                d1[d1[:, 1] == 0, 1] = 1.0  # (sign 0: no push, through a zero force below)
+            F1 = np.ones(B) if planar else np.abs(sign.cpu().numpy())
+            st = step.cpu().numpy() if isinstance(step, torch.Tensor) else step
+            push = Push(F1, d1, st, duration=D, profile=w)
+            launch = plan.rollout_launcher(zmax_t, zmin_t, x0, push=push, mass=self.config.m)
+            amp1 = launch.push_amp.clone()  # [B, C] for 1 N
+        elif fused:
             launch = plan.rollout_metrics_launcher(zmax_t, zmin_t, x0, kick=kick, kick_step=step,
                                                    lengths=lengths, out=metrics)
         else:
@@ -403,7 +465,10 @@ class ZMPController:
         dt, mass = self.config.dt, self.config.m
 
         def passes(F):
-            kick.copy_(dt * (sign * F) / mass)  # zmp_controller.py:106
+            if shove:
+                launch.push_amp.copy_(amp1 * F[:, None])
+            else:
+                kick.copy_(dt * (sign * F) / mass)  # zmp_controller.py:106
             launch()
             if not fused:
                 plan.walk_metrics(launch.hist, zmax_t, zmin_t, lengths=lengths, out=metrics)

@@ -165,12 +165,36 @@ class Plan:
         _native.check(rc, "zmpc_step")
         return out, st
 
-    def rollout_launcher(self, zmax, zmin, x0, kick=None, kick_step=-1, hist=None, status=None):
+    def _push_struct(self, push, mass, B):
+        """An analysis.Push as the C-ABI takes it: (_native.ZmpcPush, the device tensors it points
+        to).  The amplitudes need the robot's mass (the plan holds dt, not m)."""
+        from .analysis import AXES, Push
+        if not isinstance(push, Push):
+            raise ValueError(f"push must be an analysis.Push, got {type(push).__name__}")
+        if mass is None or not (float(mass) > 0) or not np.isfinite(float(mass)):
+            raise ValueError("a push needs the robot's mass in kg (mass=), finite and positive")
+        dev = self._dev()
+        amp = torch.as_tensor(push.amplitudes(self.dt, float(mass), B), device=dev)
+        prof = None if push.profile is None else torch.as_tensor(push.profile, device=dev)
+        if isinstance(push.step, int):
+            step, steps = push.step, None
+        else:
+            step = -1
+            steps = torch.as_tensor(np.broadcast_to(push.step, (B,)).copy(), device=dev)
+        c = _native.ZmpcPush(amp.data_ptr(), AXES[push.axes],
+                             None if steps is None else steps.data_ptr(), step,
+                             None if prof is None else prof.data_ptr(), push.duration)
+        return c, (amp, steps, prof)
+
+    def rollout_launcher(self, zmax, zmin, x0, kick=None, kick_step=-1, hist=None, status=None,
+                         push=None, mass=None):
         """Validate once and return a zero-argument callable that re-issues the same rollout
         launch on the current stream (one ctypes call, no tensor checks): for timing loops
-        and graph capture.  The tensors must stay alive while the launcher is used."""
+        and graph capture.  The tensors must stay alive while the launcher is used.  push, mass:
+        as rollout; launch.push_amp is then the [B, C] amplitude tensor the launch reads (write
+        new amplitudes into it between launches, as critical_force does)."""
         hist, status, (name, args, keep) = self._rollout_args(zmax, zmin, x0, kick, kick_step,
-                                                              hist, status)
+                                                              hist, status, push, mass)
         fn = getattr(_native.load(), name)
         dev = self.device
 
@@ -180,12 +204,17 @@ class Plan:
             if rc != 0:
                 _native.check(rc, name)
         launch.hist, launch.status, launch.inputs = hist, status, keep
+        launch.push_amp = keep[-1][0] if push is not None else None
         return launch
 
-    def rollout(self, zmax, zmin, x0, kick=None, kick_step=-1, hist=None, status=None):
-        """Batched Wieber rollout → hist [B,n,2,3] (device), status [B] (see _rollout_args)."""
+    def rollout(self, zmax, zmin, x0, kick=None, kick_step=-1, hist=None, status=None,
+                push=None, mass=None):
+        """Batched Wieber rollout → hist [B,n,2,3] (device), status [B] (see _rollout_args).
+        push: an analysis.Push — a shove of any length, shape and direction instead of the
+        one-sample y kick (zmpc_rollout_pushed; not together with kick); mass: the robot's mass
+        in kg, needed with push."""
         hist, status, (name, args, _) = self._rollout_args(zmax, zmin, x0, kick, kick_step, hist,
-                                                           status)
+                                                           status, push, mass)
         with torch.cuda.device(self.device):
             stream = torch.cuda.current_stream(self.device).cuda_stream
             rc = getattr(_native.load(), name)(*args, ctypes.c_void_p(stream))
@@ -211,7 +240,7 @@ class Plan:
             raise ValueError(f"z_max must be [B, n, 2] or [n, 2], got {tuple(zmax.shape)}")
         return zmax, zmin, x0, B, n, bstride
 
-    def _rollout_args(self, zmax, zmin, x0, kick, kick_step, hist, status):
+    def _rollout_args(self, zmax, zmin, x0, kick, kick_step, hist, status, push=None, mass=None):
         """Batched Wieber rollout → hist [B,n,2,3] (device), status [B].
 
         zmax/zmin: [B,n,2] per-walk CoP bounds, or [n,2] one CoP shared by every walk;
@@ -228,6 +257,13 @@ class Plan:
                              "plan's device")
         if status is None:
             status = torch.empty(B, dtype=torch.int32, device=self._dev())
+        if push is not None:
+            if kick is not None:
+                raise ValueError("give either kick or push, not both")
+            c, keep = self._push_struct(push, mass, B)
+            args = (self._live(), B, n, _ptr(zmax), _ptr(zmin), bstride, _ptr(x0),
+                    ctypes.addressof(c), _ptr(hist), _ptr(status))
+            return hist, status, ("zmpc_rollout_pushed", args, (zmax, zmin, x0, c, keep))
         if isinstance(kick_step, (int, np.integer)):
             args = (self._live(), B, n, _ptr(zmax), _ptr(zmin), bstride, _ptr(x0), _ptr(kick_t),
                     int(kick_step), _ptr(hist), _ptr(status))
@@ -448,12 +484,14 @@ class Plan:
         return out, status
 
     # -- Herdt joint footstep QP (zmpc_herdt_rollout / zmpc_herdt_step) --------------------
-    def herdt_rollout(self, params, v_ref, states, nb_next, x0, kick=None, kick_step=-1):
+    def herdt_rollout(self, params, v_ref, states, nb_next, x0, kick=None, kick_step=-1,
+                      push=None, mass=None):
         """Batched generate_com_trajectory_herdt → (hist [B,n,2,3], foot [B,n,2], status [B]).
 
         v_ref [B,n,2] or a shared [n,2]; states [B,n] or [n] int8 codes; nb_next [B,n] or [n]
         int32 (find_nb_steps of the padded states, first element); x0 [B,2,3]; kick [B] or
         None: y-velocity impulse at kick_step.  params: controllers.herdt.HerdtParams.
+        push: an analysis.Push instead of the kick (zmpc_herdt_rollout_pushed), with mass in kg.
         """
         x0 = self._as_dev(x0)
         if x0.dim() != 3 or x0.shape[1:] != (2, 3):
@@ -486,6 +524,19 @@ class Plan:
         hist = torch.empty((B, n, 2, 3), dtype=torch.float64, device=dev)
         foot = torch.empty((B, n, 2), dtype=torch.float64, device=dev)
         status = torch.empty(B, dtype=torch.int32, device=dev)
+        if push is not None:
+            if kick is not None:
+                raise ValueError("give either kick or push, not both")
+            c, keep = self._push_struct(push, mass, B)
+            with torch.cuda.device(self.device):
+                stream = torch.cuda.current_stream(self.device).cuda_stream
+                rc = _native.load().zmpc_herdt_rollout_pushed(
+                    self._live(), ctypes.byref(params), B, n, _ptr(v), vs, _ptr(st), ss, _ptr(nb),
+                    ns, _ptr(x0), ctypes.byref(c), _ptr(hist), _ptr(foot), _ptr(status),
+                    ctypes.c_void_p(stream))
+            del keep
+            _native.check(rc, "zmpc_herdt_rollout_pushed")
+            return hist, foot, status
         with torch.cuda.device(self.device):
             stream = torch.cuda.current_stream(self.device).cuda_stream
             rc = _native.load().zmpc_herdt_rollout(
