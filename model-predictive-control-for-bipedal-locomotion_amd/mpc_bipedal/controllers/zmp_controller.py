@@ -39,6 +39,21 @@ _ST_MAXITER = 1  # include/zmpc.h ZMPC_ST_MAXITER
 _ST_INFEASIBLE = 8  # include/zmpc.h ZMPC_ST_INFEASIBLE
 
 
+def _default_force_step(n, lengths):
+    """Where the push lands when no force_step is given: history step n // 2, or n_b // 2 of
+    each ragged walk (lengths [B] tensor), as zmp_controller.py:90."""
+    return n // 2 if lengths is None else lengths // 2
+
+
+def _direction_size(direction, unit):
+    """direction as an argument that sizes the scenario batch (_scenario's `sized`): a sign or
+    [B] signs as given; planar directions (unit [K, 2], else None) count as a [K] argument when
+    K > 1, one scenario each."""
+    if unit is None:
+        return direction
+    return unit[:, 0] if unit.shape[0] > 1 else None
+
+
 class ZMPController:
     """ZMP Controller using Model Predictive Control for bipedal locomotion."""
 
@@ -244,12 +259,9 @@ class ZMPController:
         nb = np.array([[t[0] for t in herdt.find_nb_steps(p)][:n] for p in pad], np.int32)
         if st.ndim == 1:
             nb = nb[0]
-        if push is not None:
-            hist, foot, status = plan.herdt_rollout(prm, v_ref, st, nb, x0, push=push,
-                                                    mass=self.config.m)
-        else:
-            hist, foot, status = plan.herdt_rollout(prm, v_ref, st, nb, x0, kick=kick,
-                                                    kick_step=kick_step)
+        hist, foot, status = plan.herdt_rollout(prm, v_ref, st, nb, x0, kick=kick,
+                                                kick_step=kick_step, push=push,
+                                                mass=self.config.m)
         if check:
             self._herdt_status(status)
         return hist, foot, status
@@ -279,39 +291,60 @@ class ZMPController:
         if push is not None and (force_step is not None or walk_lengths is not None):
             raise ValueError("a push carries its own start step(s): force_step and walk_lengths "
                              "belong to F_ext")
-        plan, zmax_t, x0, kick, step = self._batch_inputs(x_init, z_max, F_ext, force_step,
-                                                          walk_lengths)
+        plan, zmax_t, zmin_t, x0, kick, step = self._batch_inputs(x_init, z_max, z_min, F_ext,
+                                                                  force_step, walk_lengths)
         if push is not None:
             if x_init is None and zmax_t.dim() == 2 and push.batch():
                 x0 = x0.expand(push.batch(), 2, 3).contiguous()
-            hist, st = plan.rollout(zmax_t, z_min, x0, push=push, mass=self.config.m)
+            hist, st = plan.rollout(zmax_t, zmin_t, x0, push=push, mass=self.config.m)
         else:
-            hist, st = plan.rollout(zmax_t, z_min, x0, kick=kick, kick_step=step)
+            hist, st = plan.rollout(zmax_t, zmin_t, x0, kick=kick, kick_step=step)
         if plan.strict:
             self._raise_on_status(st)
         return hist, st
 
-    def _batch_inputs(self, x_init, z_max, F_ext, force_step, walk_lengths):
-        """Device inputs of the batch methods: (plan, z_max, x0, kick, kick step(s))."""
-        plan = self._plan()
-        dev = torch.device("cuda", plan.device)
-        zmax_t = torch.as_tensor(z_max, dtype=torch.float64, device=dev)
-        n = int(zmax_t.shape[-2])
-        if x_init is None:
-            B = 1 if zmax_t.dim() == 2 else int(zmax_t.shape[0])
-            x0 = torch.zeros((B, 2, 3), dtype=torch.float64, device=dev)
-        else:
-            x0 = torch.as_tensor(x_init, dtype=torch.float64, device=dev)
+    def _scenario(self, plan, z_max, z_min, x_init, walk_lengths, sized=(), planar=False):
+        """The scenario batch of the batch and robustness methods on plan's device:
+        (z_max, z_min, x0 [B,2,3], B, n, lengths [B] or None).  B comes from x_init, else from
+        per-walk bounds [B,n,2], else from the first [B] argument of `sized` (the arguments that
+        may be scalars or [B]), else it is 1; x_init None gives zero states.  A [B'] argument of
+        `sized` with B' != B raises ValueError, with planar=True in critical_force's wording."""
+        f64 = dict(dtype=torch.float64, device=torch.device("cuda", plan.device))
+        zmax_t = torch.as_tensor(z_max, **f64).contiguous()
+        zmin_t = torch.as_tensor(z_min, **f64).contiguous()
+        sizes = [int(np.shape(a)[0]) for a in sized if a is not None and np.ndim(a) == 1]
+        if x_init is not None:
+            x0 = torch.as_tensor(x_init, **f64)
             B = int(x0.shape[0])
+        else:
+            B = int(zmax_t.shape[0]) if zmax_t.dim() == 3 else (sizes[0] if sizes else 1)
+            x0 = torch.zeros((B, 2, 3), **f64)
+        if any(s != B for s in sizes):
+            raise ValueError("force_step, direction and walk_lengths must be scalars or "
+                             f"[B] = [{B}]"
+                             + (" (planar directions [1, 2] or [B, 2])" if planar else ""))
+        lengths = None
+        if walk_lengths is not None:
+            lengths = torch.as_tensor(walk_lengths, dtype=torch.int64,
+                                      device=f64["device"]).reshape(B)
+        return zmax_t, zmin_t, x0, B, int(zmax_t.shape[-2]), lengths
+
+    def _batch_inputs(self, x_init, z_max, z_min, F_ext, force_step, walk_lengths):
+        """Device inputs of the batch methods: (plan, z_max, z_min, x0, kick, kick step(s)).
+        Only x_init and per-walk bounds size the batch; with walk_lengths the kick hits n_b // 2
+        whatever force_step says."""
+        plan = self._plan()
+        zmax_t, zmin_t, x0, B, n, lengths = self._scenario(plan, z_max, z_min, x_init,
+                                                           walk_lengths)
         kick = None
         if F_ext is not None:
-            F = torch.as_tensor(F_ext, dtype=torch.float64, device=dev).reshape(B)
+            F = torch.as_tensor(F_ext, dtype=torch.float64, device=x0.device).reshape(B)
             kick = self.config.dt * F / self.config.m
-        if walk_lengths is not None:
-            step = torch.as_tensor(walk_lengths, dtype=torch.int64, device=dev).reshape(B) // 2
+        if lengths is not None or force_step is None:
+            step = _default_force_step(n, lengths)
         else:
-            step = (n // 2) if force_step is None else int(force_step)
-        return plan, zmax_t, x0, kick, step
+            step = int(force_step)
+        return plan, zmax_t, zmin_t, x0, kick, step
 
     def generate_walk_metrics_batch(self, x_init, z_max, z_min, F_ext=None,
                                     force_step: Optional[int] = None, walk_lengths=None):
@@ -321,9 +354,9 @@ class ZMPController:
         device's registers instead of n·48.  With walk_lengths the metrics cover each walk's own
         n_b samples.  Returns (analysis.WalkMetrics, status [B]) on the plan's device.  Strict
         plans and walks of more than 513 samples run the two launches behind the same call."""
-        plan, zmax_t, x0, kick, step = self._batch_inputs(x_init, z_max, F_ext, force_step,
-                                                          walk_lengths)
-        m, st = plan.rollout_metrics(zmax_t, z_min, x0, kick=kick, kick_step=step,
+        plan, zmax_t, zmin_t, x0, kick, step = self._batch_inputs(x_init, z_max, z_min, F_ext,
+                                                                  force_step, walk_lengths)
+        m, st = plan.rollout_metrics(zmax_t, zmin_t, x0, kick=kick, kick_step=step,
                                      lengths=walk_lengths)
         if plan.strict:
             self._raise_on_status(st)
@@ -410,34 +443,17 @@ class ZMPController:
         plan = self._plan()
         dev = torch.device("cuda", plan.device)
         f64 = dict(dtype=torch.float64, device=dev)
-        zmax_t = torch.as_tensor(z_max, **f64).contiguous()
-        zmin_t = torch.as_tensor(z_min, **f64).contiguous()
-        n = int(zmax_t.shape[-2])
-        sizes = [int(np.shape(a)[0]) for a in (force_step, walk_lengths) + (() if planar else
-                                                                            (direction,))
-                 if a is not None and np.ndim(a) == 1]
-        if planar and unit.shape[0] > 1:  # K > 1 planar directions: one scenario each
-            sizes.append(int(unit.shape[0]))
-        if x_init is not None:
-            x0 = torch.as_tensor(x_init, **f64)
-            B = int(x0.shape[0])
-        else:
-            B = int(zmax_t.shape[0]) if zmax_t.dim() == 3 else (sizes[0] if sizes else 1)
-            x0 = torch.zeros((B, 2, 3), **f64)
-        if any(s != B for s in sizes):
-            raise ValueError("force_step, direction and walk_lengths must be scalars or "
-                             f"[B] = [{B}] (planar directions [1, 2] or [B, 2])")
+        zmax_t, zmin_t, x0, B, n, lengths = self._scenario(
+            plan, z_max, z_min, x_init, walk_lengths,
+            sized=(force_step, walk_lengths, _direction_size(direction, unit)), planar=True)
         if not (F_hi > 0) or iters < 0:
             raise ValueError("need F_hi > 0 and iters >= 0")
         if planar:
             sign = None
         else:
             sign = torch.sign(torch.as_tensor(direction, **f64)).expand(B).contiguous()
-        lengths = None
-        if walk_lengths is not None:
-            lengths = torch.as_tensor(walk_lengths, dtype=torch.int64, device=dev).reshape(B)
         if force_step is None:
-            step = (n // 2) if lengths is None else lengths // 2
+            step = _default_force_step(n, lengths)
         elif np.ndim(force_step) == 0:
             step = int(force_step)
         else:
@@ -500,24 +516,8 @@ class ZMPController:
             raise RuntimeError("the push map needs the unconstrained controller: the ZMP response "
                                "of a strict (clamped) plan is not affine in the push — use "
                                "critical_force")
-        dev = torch.device("cuda", plan.device)
-        f64 = dict(dtype=torch.float64, device=dev)
-        zmax_t = torch.as_tensor(z_max, **f64).contiguous()
-        zmin_t = torch.as_tensor(z_min, **f64).contiguous()
-        n = int(zmax_t.shape[-2])
-        sizes = [int(np.shape(a)[0]) for a in (*extra, walk_lengths)
-                 if a is not None and np.ndim(a) == 1]
-        if x_init is not None:
-            x0 = torch.as_tensor(x_init, **f64)
-            B = int(x0.shape[0])
-        else:
-            B = int(zmax_t.shape[0]) if zmax_t.dim() == 3 else (sizes[0] if sizes else 1)
-            x0 = torch.zeros((B, 2, 3), **f64)
-        if any(s != B for s in sizes):
-            raise ValueError(f"force_step, direction and walk_lengths must be scalars or [B] = [{B}]")
-        lengths = None
-        if walk_lengths is not None:
-            lengths = torch.as_tensor(walk_lengths, dtype=torch.int64, device=dev).reshape(B)
+        zmax_t, zmin_t, x0, B, n, lengths = self._scenario(plan, z_max, z_min, x_init,
+                                                           walk_lengths, (*extra, walk_lengths))
         hist, _ = plan.rollout(zmax_t, zmin_t, x0)
         return plan, hist, zmax_t, zmin_t, lengths, B, n
 
@@ -562,20 +562,14 @@ class ZMPController:
         two signs): the result is then the critical magnitude of a push along that direction,
         from the x and y tables of one launch (analysis.planar_push)."""
         planar = np.ndim(direction) == 2
-        if planar:
-            unit = unit_directions(direction)
-            # (K > 1 directions count as a [K] argument: one scenario each)
-            extra = (force_step,) + ((unit[:, 0],) if unit.shape[0] > 1 else ())
-        else:
-            extra = (force_step, direction)
+        unit = unit_directions(direction) if planar else None
         plan, hist, zmax_t, zmin_t, lengths, B, n = self._unpushed(
-            z_max, z_min, x_init, walk_lengths, extra=extra)
+            z_max, z_min, x_init, walk_lengths,
+            extra=(force_step, _direction_size(direction, unit)))
         dev = hist.device
         if force_step is None:
-            step = torch.full((B,), n // 2, dtype=torch.int64, device=dev) if lengths is None \
-                else lengths // 2
-        else:
-            step = torch.as_tensor(force_step, dtype=torch.int64, device=dev).expand(B)
+            force_step = _default_force_step(n, lengths)
+        step = torch.as_tensor(force_step, dtype=torch.int64, device=dev).expand(B)
         force, limit = plan.push_map(hist, zmax_t, zmin_t, lengths=lengths,
                                      push_steps=step.contiguous(), max_violation=max_violation,
                                      mass=self.config.m, duration=duration, profile=profile,

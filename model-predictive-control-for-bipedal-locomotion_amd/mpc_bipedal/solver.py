@@ -22,6 +22,11 @@ from .models.lipm_model import plan_constants
 _PLAN_CACHE = OrderedDict()
 PLAN_CACHE_MAX = max(1, int(os.environ.get("ZMPC_PLAN_CACHE", "8")))
 
+# what Plan._out raises for a state history and for a metrics tensor
+_HIST_MSG = "hist must be a contiguous float64 [B, n, 2, 3] tensor on the plan's device"
+_METRICS_MSG = (f"out must be a contiguous float64 [B, {_native.NMETRICS}] tensor on the plan's "
+                "device")
+
 
 def _device_index(backend: str) -> int:
     if not torch.cuda.is_available():
@@ -46,18 +51,16 @@ class Plan:
                  strict: bool):
         lib = _native.load()
         self.device = int(device)
+        self._device = torch.device("cuda", self.device)
         self.N = int(N)
         self.dt, self.h, self.g, self.Q, self.R = float(dt), float(h), float(g), float(Q), float(R)
         self.strict = bool(strict)
         c = plan_constants(self.dt, self.h, self.g)
         self.consts = c
         handle = ctypes.c_void_p()
-        with torch.cuda.device(self.device):
-            stream = torch.cuda.current_stream(self.device).cuda_stream
-            rc = lib.zmpc_plan_create(self.device, self.N, c["T"], c["T2_2"], c["T3_6"], c["hg"],
-                                      c["Thg"], self.Q, self.R, int(self.strict),
-                                      ctypes.c_void_p(stream), ctypes.byref(handle))
-        _native.check(rc, "zmpc_plan_create")
+        _native.call("zmpc_plan_create", self.device, self.device, self.N, c["T"], c["T2_2"],
+                     c["T3_6"], c["hg"], c["Thg"], self.Q, self.R, int(self.strict),
+                     after=(ctypes.byref(handle),))
         self._h = handle
         self._finalizer = weakref.finalize(self, lib.zmpc_plan_destroy, handle)
 
@@ -78,27 +81,21 @@ class Plan:
             self._h = None
 
     def export(self, what: int) -> np.ndarray:
-        """A plan quantity on the host (zmpc_plan_export, ids _native.EXPORT_*).  Matrices come
-        back [N, N], Px [N, 3], the fast-FIR taps [rows, 4], the FFT tables complex."""
-        n = {0: self.N, 1: 3 * self.N, 2: self.N ** 2, 3: self.N, 4: 3, 5: self.N ** 2,
-             6: self.N ** 2, 7: self.N ** 2, 8: 4 * _native.kffa_rows(self.N),
-             9: _native.ksum_rows(self.N), 10: _native.SCAN_DOUBLES, 11: self.N ** 2,
-             12: self.N, 13: 2 * _native.FFT_PT, 14: 2 * _native.FFT_G_COMPLEX}.get(what)
-        if n is None:
+        """A plan quantity on the host (zmpc_plan_export, ids _native.EXPORT_*, table
+        _native.EXPORTS).  Matrices come back [N, N], Px [N, 3], the fast-FIR taps [rows, 4], the
+        FFT tables complex."""
+        entry = _native.EXPORTS.get(what)
+        if entry is None:
             raise ValueError(f"zmpc_plan_export: unknown export id {what}")
+        _, count, shape = entry
+        n = count(self.N)
         buf = np.empty(n, dtype=np.float64)
         rc = _native.load().zmpc_plan_export(
             self._live(), what, buf.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), n)
         _native.check(rc, "zmpc_plan_export")
-        if what in (1,):
-            return buf.reshape(self.N, 3)
-        if what in (2, 5, 6, 7, 11):
-            return buf.reshape(self.N, self.N)
-        if what == 8:
-            return buf.reshape(-1, 4)
-        if what in (13, 14):
+        if shape is complex:
             return buf.view(np.complex128)
-        return buf
+        return buf if shape is None else buf.reshape(shape(self.N))
 
     def counters(self, reset: bool = False) -> dict:
         """Active-set solver work counters (zmpc_plan_counters, include/zmpc.h), summed over this
@@ -107,11 +104,7 @@ class Plan:
         buf = (ctypes.c_uint64 * _native.NCOUNTERS)()
         rc = _native.load().zmpc_plan_counters(self._live(), buf, _native.NCOUNTERS, int(reset))
         _native.check(rc, "zmpc_plan_counters")
-        return {"wave_passes": int(buf[0]), "instance_passes": int(buf[1]),
-                "working_set_slots": int(buf[2]), "launches": int(buf[3]),
-                "herdt_wave_passes": int(buf[4]), "herdt_instance_passes": int(buf[5]),
-                "herdt_footsteps": int(buf[6]), "herdt_footsteps_sq": int(buf[7]),
-                "max_passes_per_solve": int(buf[8]), "herdt_max_passes_per_solve": int(buf[9])}
+        return {name: int(v) for name, v in zip(_native.COUNTER_NAMES, buf)}
 
     def set_option(self, option, value: int) -> "Plan":
         """zmpc_plan_set_option: choose between forms that compute the same solution (cross-checks
@@ -137,43 +130,91 @@ class Plan:
         _native.check(rc, "zmpc_plan_timings")
         return {name: float(buf[i]) for i, name in enumerate(_native.PLAN_STAGE_NAMES)}
 
-    # -- launches --------------------------------------------------------------------------
-    def _dev(self):
-        return torch.device("cuda", self.device)
-
+    # -- checked arguments: each rule of the launch methods, stated once --------------------
     def _as_dev(self, a, shape=None):
-        t = torch.as_tensor(a, dtype=torch.float64, device=self._dev())
+        t = torch.as_tensor(a, dtype=torch.float64, device=self._device)
         t = t.contiguous()
         if shape is not None and tuple(t.shape) != tuple(shape):
             raise ValueError(f"expected shape {tuple(shape)}, got {tuple(t.shape)}")
         return t
 
-    def step(self, x, zmax_win, zmin_win, status=None):
-        """Batched predict_wieber_axis: x [B,3], windows [B,N] → x_next [B,3] (device)."""
-        x = self._as_dev(x)
-        B = x.shape[0]
-        zmax_win = self._as_dev(zmax_win, (B, self.N))
-        zmin_win = self._as_dev(zmin_win, (B, self.N))
-        x = x.reshape(B, 3)
-        out = torch.empty((B, 3), dtype=torch.float64, device=self._dev())
-        st = status if status is not None else torch.empty(B, dtype=torch.int32,
-                                                           device=self._dev())
-        with torch.cuda.device(self.device):
-            stream = torch.cuda.current_stream(self.device).cuda_stream
-            rc = _native.load().zmpc_step(self._live(), B, _ptr(x), _ptr(zmax_win), _ptr(zmin_win),
-                                          _ptr(out), _ptr(st), ctypes.c_void_p(stream))
-        _native.check(rc, "zmpc_step")
-        return out, st
+    def _x0(self, x0):
+        """Initial states on the device and the batch size they set: (x0 [B, 2, 3], B)."""
+        x0 = self._as_dev(x0)
+        if x0.dim() != 3 or x0.shape[1:] != (2, 3):
+            raise ValueError(f"x0 must be [B, 2, 3], got {tuple(x0.shape)}")
+        return x0, int(x0.shape[0])
 
-    def _push_struct(self, push, mass, B):
+    def _hist_dims(self, hist):
+        """(B, n) of a state history: a contiguous float64 [B, n, 2, 3] tensor on the plan's
+        device with n >= 1, which is never copied."""
+        if not isinstance(hist, torch.Tensor) or hist.dim() != 4 or hist.shape[2:] != (2, 3) \
+                or hist.dtype != torch.float64 or hist.device != self._device \
+                or not hist.is_contiguous():
+            raise ValueError(_HIST_MSG)
+        if hist.shape[1] < 1:
+            raise ValueError("hist must hold at least one sample per walk")
+        return int(hist.shape[0]), int(hist.shape[1])
+
+    def _out(self, t, shape, dtype, msg):
+        """An output to write into: t if it is a contiguous `dtype` tensor of `shape` on the
+        plan's device (ValueError(msg) otherwise), a new one for None."""
+        if t is None:
+            return torch.empty(shape, dtype=dtype, device=self._device)
+        if tuple(t.shape) != tuple(shape) or t.dtype != dtype or t.device != self._device or \
+                not t.is_contiguous():
+            raise ValueError(msg)
+        return t
+
+    def _bounds(self, zmax, zmin, B, n=None):
+        """CoP bounds on the device → (zmax, zmin, stride between walks): [B, n, 2] per walk
+        (stride 2n), or [n, 2] one CoP shared by every walk (stride 0).  With n, both B and n are
+        a history's and the message names them; n None: a rollout's bounds, which set n
+        themselves (B is x0's)."""
+        zmax = self._as_dev(zmax)
+        if n is not None:
+            shape = (n, 2) if zmax.dim() == 2 else (B, n, 2)
+            if tuple(zmax.shape) != shape:
+                raise ValueError(f"z_max must be [B, n, 2] = [{B}, {n}, 2] or [n, 2], got "
+                                 f"{tuple(zmax.shape)}")
+        elif (zmax.dim() == 2 and zmax.shape[1] == 2) or \
+                (zmax.dim() == 3 and zmax.shape[2] == 2 and zmax.shape[0] == B):
+            shape = tuple(zmax.shape)
+        else:
+            raise ValueError(f"z_max must be [B, n, 2] or [n, 2], got {tuple(zmax.shape)}")
+        return zmax, self._as_dev(zmin, shape), 0 if zmax.dim() == 2 else 2 * shape[1]
+
+    def _index(self, a, B, name, sized=True):
+        """An optional [B] index array as an int64 tensor on the device (None stays None).
+        Raises e.g. "lengths must be [B] = [4], got (3,)"; sized=False leaves the "= [4]" out."""
+        if a is None:
+            return None
+        t = torch.as_tensor(a, dtype=torch.int64, device=self._device).contiguous()
+        if tuple(t.shape) != (B,):
+            raise ValueError(f"{name} must be [B]{f' = [{B}]' if sized else ''}, got "
+                             f"{tuple(t.shape)}")
+        return t
+
+    def _kick(self, kick, kick_step, B):
+        """The one-sample y kick as the C-ABI takes it: (kick [B] tensor or None, scalar step,
+        per-walk steps).  kick_step an int: (.., step, None); a [B] array: (.., −1, tensor)."""
+        kick_t = None if kick is None else self._as_dev(kick, (B,))
+        if isinstance(kick_step, (int, np.integer)):
+            return kick_t, int(kick_step), None
+        return kick_t, -1, self._index(kick_step, B, "per-walk kick_step", sized=False)
+
+    def _push_struct(self, push, mass, B, kick=None):
         """An analysis.Push as the C-ABI takes it: (_native.ZmpcPush, the device tensors it points
-        to).  The amplitudes need the robot's mass (the plan holds dt, not m)."""
+        to).  The amplitudes need the robot's mass (the plan holds dt, not m).  kick: the
+        caller's one-sample kick, which a push excludes."""
         from .analysis import AXES, Push
+        if kick is not None:
+            raise ValueError("give either kick or push, not both")
         if not isinstance(push, Push):
             raise ValueError(f"push must be an analysis.Push, got {type(push).__name__}")
         if mass is None or not (float(mass) > 0) or not np.isfinite(float(mass)):
             raise ValueError("a push needs the robot's mass in kg (mass=), finite and positive")
-        dev = self._dev()
+        dev = self._device
         amp = torch.as_tensor(push.amplitudes(self.dt, float(mass), B), device=dev)
         prof = None if push.profile is None else torch.as_tensor(push.profile, device=dev)
         if isinstance(push.step, int):
@@ -186,6 +227,36 @@ class Plan:
                              None if prof is None else prof.data_ptr(), push.duration)
         return c, (amp, steps, prof)
 
+    # -- launches --------------------------------------------------------------------------
+    def _launcher(self, name, args, **attrs):
+        """A zero-argument callable that re-issues name(*args, current stream) and carries
+        attrs.  One launch is one stream lookup and one ctypes call: no device context, no
+        argument work, and _native.check only on a nonzero return."""
+        fn = getattr(_native.load(), name)
+        dev = self.device
+
+        def launch():
+            stream = torch.cuda.current_stream(dev).cuda_stream
+            rc = fn(*args, ctypes.c_void_p(stream))
+            if rc != 0:
+                _native.check(rc, name)
+        launch.__dict__.update(attrs)
+        return launch
+
+    def step(self, x, zmax_win, zmin_win, status=None):
+        """Batched predict_wieber_axis: x [B,3], windows [B,N] → x_next [B,3] (device)."""
+        x = self._as_dev(x)
+        B = x.shape[0]
+        zmax_win = self._as_dev(zmax_win, (B, self.N))
+        zmin_win = self._as_dev(zmin_win, (B, self.N))
+        x = x.reshape(B, 3)
+        out = torch.empty((B, 3), dtype=torch.float64, device=self._device)
+        st = status if status is not None else torch.empty(B, dtype=torch.int32,
+                                                           device=self._device)
+        _native.call("zmpc_step", self.device, self._live(), B, _ptr(x), _ptr(zmax_win),
+                     _ptr(zmin_win), _ptr(out), _ptr(st))
+        return out, st
+
     def rollout_launcher(self, zmax, zmin, x0, kick=None, kick_step=-1, hist=None, status=None,
                          push=None, mass=None):
         """Validate once and return a zero-argument callable that re-issues the same rollout
@@ -195,17 +266,8 @@ class Plan:
         new amplitudes into it between launches, as critical_force does)."""
         hist, status, (name, args, keep) = self._rollout_args(zmax, zmin, x0, kick, kick_step,
                                                               hist, status, push, mass)
-        fn = getattr(_native.load(), name)
-        dev = self.device
-
-        def launch():
-            stream = torch.cuda.current_stream(dev).cuda_stream
-            rc = fn(*args, ctypes.c_void_p(stream))
-            if rc != 0:
-                _native.check(rc, name)
-        launch.hist, launch.status, launch.inputs = hist, status, keep
-        launch.push_amp = keep[-1][0] if push is not None else None
-        return launch
+        return self._launcher(name, args, hist=hist, status=status, inputs=keep,
+                              push_amp=keep[-1][0] if push is not None else None)
 
     def rollout(self, zmax, zmin, x0, kick=None, kick_step=-1, hist=None, status=None,
                 push=None, mass=None):
@@ -215,30 +277,14 @@ class Plan:
         in kg, needed with push."""
         hist, status, (name, args, _) = self._rollout_args(zmax, zmin, x0, kick, kick_step, hist,
                                                            status, push, mass)
-        with torch.cuda.device(self.device):
-            stream = torch.cuda.current_stream(self.device).cuda_stream
-            rc = getattr(_native.load(), name)(*args, ctypes.c_void_p(stream))
-        _native.check(rc, name)
+        _native.call(name, self.device, *args)
         return hist, status
 
     def _walk_inputs(self, zmax, zmin, x0):
         """The walks of a rollout on the device: (zmax, zmin, x0, B, n, bounds stride)."""
-        zmax = self._as_dev(zmax)
-        x0 = self._as_dev(x0)
-        if x0.dim() != 3 or x0.shape[1:] != (2, 3):
-            raise ValueError(f"x0 must be [B, 2, 3], got {tuple(x0.shape)}")
-        B = int(x0.shape[0])
-        if zmax.dim() == 2 and zmax.shape[1] == 2:
-            n = int(zmax.shape[0])
-            zmin = self._as_dev(zmin, (n, 2))
-            bstride = 0
-        elif zmax.dim() == 3 and zmax.shape[2] == 2 and zmax.shape[0] == B:
-            n = int(zmax.shape[1])
-            zmin = self._as_dev(zmin, (B, n, 2))
-            bstride = 2 * n
-        else:
-            raise ValueError(f"z_max must be [B, n, 2] or [n, 2], got {tuple(zmax.shape)}")
-        return zmax, zmin, x0, B, n, bstride
+        x0, B = self._x0(x0)
+        zmax, zmin, bstride = self._bounds(zmax, zmin, B)
+        return zmax, zmin, x0, B, int(zmax.shape[-2]), bstride
 
     def _rollout_args(self, zmax, zmin, x0, kick, kick_step, hist, status, push=None, mass=None):
         """Batched Wieber rollout → hist [B,n,2,3] (device), status [B].
@@ -246,34 +292,25 @@ class Plan:
         zmax/zmin: [B,n,2] per-walk CoP bounds, or [n,2] one CoP shared by every walk;
         x0: [B,2,3]; kick: [B] velocity impulse subtracted from y at step kick_step — an int,
         or a [B] array of per-walk steps (ragged walks: zmpc_rollout_kicks).
+        Returns (hist, status, (symbol, its arguments without the stream, what they point to)).
         """
         zmax, zmin, x0, B, n, bstride = self._walk_inputs(zmax, zmin, x0)
-        kick_t = None if kick is None else self._as_dev(kick, (B,))
-        if hist is None:
-            hist = torch.empty((B, n, 2, 3), dtype=torch.float64, device=self._dev())
-        elif tuple(hist.shape) != (B, n, 2, 3) or hist.dtype != torch.float64 or \
-                hist.device != self._dev() or not hist.is_contiguous():
-            raise ValueError("hist must be a contiguous float64 [B, n, 2, 3] tensor on the "
-                             "plan's device")
+        hist = self._out(hist, (B, n, 2, 3), torch.float64, _HIST_MSG)
         if status is None:
-            status = torch.empty(B, dtype=torch.int32, device=self._dev())
+            status = torch.empty(B, dtype=torch.int32, device=self._device)
+        walks = (self._live(), B, n, _ptr(zmax), _ptr(zmin), bstride, _ptr(x0))
+        outs = (_ptr(hist), _ptr(status))
         if push is not None:
-            if kick is not None:
-                raise ValueError("give either kick or push, not both")
-            c, keep = self._push_struct(push, mass, B)
-            args = (self._live(), B, n, _ptr(zmax), _ptr(zmin), bstride, _ptr(x0),
-                    ctypes.addressof(c), _ptr(hist), _ptr(status))
-            return hist, status, ("zmpc_rollout_pushed", args, (zmax, zmin, x0, c, keep))
-        if isinstance(kick_step, (int, np.integer)):
-            args = (self._live(), B, n, _ptr(zmax), _ptr(zmin), bstride, _ptr(x0), _ptr(kick_t),
-                    int(kick_step), _ptr(hist), _ptr(status))
-            return hist, status, ("zmpc_rollout", args, (zmax, zmin, x0, kick_t))
-        ks = torch.as_tensor(kick_step, dtype=torch.int64, device=self._dev()).contiguous()
-        if tuple(ks.shape) != (B,):
-            raise ValueError(f"per-walk kick_step must be [B], got {tuple(ks.shape)}")
-        args = (self._live(), B, n, _ptr(zmax), _ptr(zmin), bstride, _ptr(x0), _ptr(kick_t),
-                _ptr(ks), _ptr(hist), _ptr(status))
-        return hist, status, ("zmpc_rollout_kicks", args, (zmax, zmin, x0, kick_t, ks))
+            c, keep = self._push_struct(push, mass, B, kick)
+            # (the arguments hold the struct's address: it lives in what the launcher keeps)
+            return hist, status, ("zmpc_rollout_pushed", walks + (ctypes.addressof(c),) + outs,
+                                  (zmax, zmin, x0, c, keep))
+        kick_t, step, ks = self._kick(kick, kick_step, B)
+        if ks is None:
+            return hist, status, ("zmpc_rollout", walks + (_ptr(kick_t), step) + outs,
+                                  (zmax, zmin, x0, kick_t))
+        return hist, status, ("zmpc_rollout_kicks", walks + (_ptr(kick_t), _ptr(ks)) + outs,
+                              (zmax, zmin, x0, kick_t, ks))
 
     def walk_metrics(self, hist, zmax, zmin, lengths=None, out=None):
         """Per-walk robustness metrics of a state history (zmpc_walk_metrics, include/zmpc.h)
@@ -285,40 +322,12 @@ class Plan:
         None; out: a contiguous float64 [B, 12] tensor on the plan's device to write into.
         Asynchronous on the current stream.  Works on any plan: only h/g is read.
         """
-        dev = self._dev()
-        if not isinstance(hist, torch.Tensor) or hist.dim() != 4 or hist.shape[2:] != (2, 3) \
-                or hist.dtype != torch.float64 or hist.device != dev or not hist.is_contiguous():
-            raise ValueError("hist must be a contiguous float64 [B, n, 2, 3] tensor on the "
-                             "plan's device")
-        B, n = int(hist.shape[0]), int(hist.shape[1])
-        if n < 1:
-            raise ValueError("hist must hold at least one sample per walk")
-        zmax = self._as_dev(zmax)
-        if zmax.dim() == 2:
-            shape, bstride = (n, 2), 0
-        else:
-            shape, bstride = (B, n, 2), 2 * n
-        if tuple(zmax.shape) != shape:
-            raise ValueError(f"z_max must be [B, n, 2] = [{B}, {n}, 2] or [n, 2], got "
-                             f"{tuple(zmax.shape)}")
-        zmin = self._as_dev(zmin, shape)
-        len_t = None
-        if lengths is not None:
-            len_t = torch.as_tensor(lengths, dtype=torch.int64, device=dev).contiguous()
-            if tuple(len_t.shape) != (B,):
-                raise ValueError(f"lengths must be [B] = [{B}], got {tuple(len_t.shape)}")
-        if out is None:
-            out = torch.empty((B, _native.NMETRICS), dtype=torch.float64, device=dev)
-        elif tuple(out.shape) != (B, _native.NMETRICS) or out.dtype != torch.float64 or \
-                out.device != dev or not out.is_contiguous():
-            raise ValueError(f"out must be a contiguous float64 [B, {_native.NMETRICS}] tensor "
-                             "on the plan's device")
-        with torch.cuda.device(self.device):
-            stream = torch.cuda.current_stream(self.device).cuda_stream
-            rc = _native.load().zmpc_walk_metrics(self._live(), B, n, _ptr(hist), _ptr(zmax),
-                                                  _ptr(zmin), bstride, _ptr(len_t), _ptr(out),
-                                                  ctypes.c_void_p(stream))
-        _native.check(rc, "zmpc_walk_metrics")
+        B, n = self._hist_dims(hist)
+        zmax, zmin, bstride = self._bounds(zmax, zmin, B, n)
+        len_t = self._index(lengths, B, "lengths")
+        out = self._out(out, (B, _native.NMETRICS), torch.float64, _METRICS_MSG)
+        _native.call("zmpc_walk_metrics", self.device, self._live(), B, n, _ptr(hist),
+                     _ptr(zmax), _ptr(zmin), bstride, _ptr(len_t), _ptr(out))
         return out
 
     # -- push-robustness map (zmpc_push_map) -----------------------------------------------
@@ -342,32 +351,11 @@ class Plan:
         those shapes on the plan's device to write into.  Asynchronous on the current stream.
         Non-strict plans only: a strict plan raises NativeError (ZMPC_ESTATE), as does a full map
         of walks longer than the kernel's LDS holds (10112 samples)."""
-        dev = self._dev()
-        if not isinstance(hist, torch.Tensor) or hist.dim() != 4 or hist.shape[2:] != (2, 3) \
-                or hist.dtype != torch.float64 or hist.device != dev or not hist.is_contiguous():
-            raise ValueError("hist must be a contiguous float64 [B, n, 2, 3] tensor on the "
-                             "plan's device")
-        B, n = int(hist.shape[0]), int(hist.shape[1])
-        if n < 1:
-            raise ValueError("hist must hold at least one sample per walk")
-        zmax = self._as_dev(zmax)
-        if zmax.dim() == 2:
-            shape, bstride = (n, 2), 0
-        else:
-            shape, bstride = (B, n, 2), 2 * n
-        if tuple(zmax.shape) != shape:
-            raise ValueError(f"z_max must be [B, n, 2] = [{B}, {n}, 2] or [n, 2], got "
-                             f"{tuple(zmax.shape)}")
-        zmin = self._as_dev(zmin, shape)
-        len_t = steps_t = None
-        if lengths is not None:
-            len_t = torch.as_tensor(lengths, dtype=torch.int64, device=dev).contiguous()
-            if tuple(len_t.shape) != (B,):
-                raise ValueError(f"lengths must be [B] = [{B}], got {tuple(len_t.shape)}")
-        if push_steps is not None:
-            steps_t = torch.as_tensor(push_steps, dtype=torch.int64, device=dev).contiguous()
-            if tuple(steps_t.shape) != (B,):
-                raise ValueError(f"push_steps must be [B] = [{B}], got {tuple(steps_t.shape)}")
+        dev = self._device
+        B, n = self._hist_dims(hist)
+        zmax, zmin, bstride = self._bounds(zmax, zmin, B, n)
+        len_t = self._index(lengths, B, "lengths")
+        steps_t = self._index(push_steps, B, "push_steps")
         from .analysis import AXES, check_profile
         if axes not in AXES:
             raise ValueError(f"axes must be 'x', 'y' or 'xy', got {axes!r}")
@@ -381,60 +369,32 @@ class Plan:
         else:
             D, w = check_profile(duration, profile)
             prof_t = None if w is None else torch.as_tensor(w, device=dev)
-        shaped = D != 1 or prof_t is not None or axes != "y"
         C = 4 if axes == "xy" else 2
         oshape = (B, n, C) if steps_t is None else (B, C)
-        if out is None:
-            force = torch.empty(oshape, dtype=torch.float64, device=dev)
-            limit = torch.empty(oshape, dtype=torch.int32, device=dev)
-        else:
-            force, limit = out
-            for t, dt in ((force, torch.float64), (limit, torch.int32)):
-                if tuple(t.shape) != oshape or t.dtype != dt or t.device != dev or \
-                        not t.is_contiguous():
-                    raise ValueError(f"out must be (float64, int32) contiguous {oshape} tensors "
-                                     "on the plan's device")
+        force, limit = (None, None) if out is None else out
+        msg = out is not None and (f"out must be (float64, int32) contiguous {oshape} tensors "
+                                   "on the plan's device")
+        force = self._out(force, oshape, torch.float64, msg)
+        limit = self._out(limit, oshape, torch.int32, msg)
         resp = torch.empty(n, dtype=torch.float64, device=dev) if want_response else None
-        with torch.cuda.device(self.device):
-            stream = torch.cuda.current_stream(self.device).cuda_stream
-            if shaped:
-                rc = _native.load().zmpc_push_map_shaped(
-                    self._live(), B, n, _ptr(hist), _ptr(zmax), _ptr(zmin), bstride, _ptr(len_t),
-                    _ptr(steps_t), _ptr(prof_t), D, AXES[axes], float(max_violation), float(mass),
-                    _ptr(force), _ptr(limit), _ptr(resp), ctypes.c_void_p(stream))
-            else:
-                rc = _native.load().zmpc_push_map(self._live(), B, n, _ptr(hist), _ptr(zmax),
-                                                  _ptr(zmin), bstride, _ptr(len_t), _ptr(steps_t),
-                                                  float(max_violation), float(mass), _ptr(force),
-                                                  _ptr(limit), _ptr(resp), ctypes.c_void_p(stream))
-        _native.check(rc, "zmpc_push_map_shaped" if shaped else "zmpc_push_map")
+        walks = (self._live(), B, n, _ptr(hist), _ptr(zmax), _ptr(zmin), bstride, _ptr(len_t),
+                 _ptr(steps_t))
+        outs = (float(max_violation), float(mass), _ptr(force), _ptr(limit), _ptr(resp))
+        if D != 1 or prof_t is not None or axes != "y":
+            _native.call("zmpc_push_map_shaped", self.device, *walks, _ptr(prof_t), D,
+                         AXES[axes], *outs)
+        else:
+            _native.call("zmpc_push_map", self.device, *walks, *outs)
         return (force, limit, resp) if want_response else (force, limit)
 
     # -- fused rollout-to-metrics (zmpc_rollout_metrics) -----------------------------------
     def _rollout_metrics_args(self, zmax, zmin, x0, kick, kick_step, lengths, out, status):
-        dev = self._dev()
         zmax, zmin, x0, B, n, bstride = self._walk_inputs(zmax, zmin, x0)
-        kick_t = None if kick is None else self._as_dev(kick, (B,))
-        if isinstance(kick_step, (int, np.integer)):
-            step, ks = int(kick_step), None
-        else:
-            step = -1
-            ks = torch.as_tensor(kick_step, dtype=torch.int64, device=dev).contiguous()
-            if tuple(ks.shape) != (B,):
-                raise ValueError(f"per-walk kick_step must be [B], got {tuple(ks.shape)}")
-        len_t = None
-        if lengths is not None:
-            len_t = torch.as_tensor(lengths, dtype=torch.int64, device=dev).contiguous()
-            if tuple(len_t.shape) != (B,):
-                raise ValueError(f"lengths must be [B] = [{B}], got {tuple(len_t.shape)}")
-        if out is None:
-            out = torch.empty((B, _native.NMETRICS), dtype=torch.float64, device=dev)
-        elif tuple(out.shape) != (B, _native.NMETRICS) or out.dtype != torch.float64 or \
-                out.device != dev or not out.is_contiguous():
-            raise ValueError(f"out must be a contiguous float64 [B, {_native.NMETRICS}] tensor "
-                             "on the plan's device")
+        kick_t, step, ks = self._kick(kick, kick_step, B)
+        len_t = self._index(lengths, B, "lengths")
+        out = self._out(out, (B, _native.NMETRICS), torch.float64, _METRICS_MSG)
         if status is None:
-            status = torch.empty(B, dtype=torch.int32, device=dev)
+            status = torch.empty(B, dtype=torch.int32, device=self._device)
         args = (self._live(), B, n, _ptr(zmax), _ptr(zmin), bstride, _ptr(x0), _ptr(kick_t), step,
                 _ptr(ks), _ptr(len_t), _ptr(out), _ptr(status))
         return out, status, args, (zmax, zmin, x0, kick_t, ks, len_t)
@@ -447,16 +407,8 @@ class Plan:
         form raises NativeError at the first call."""
         out, status, args, keep = self._rollout_metrics_args(zmax, zmin, x0, kick, kick_step,
                                                              lengths, out, status)
-        fn = _native.load().zmpc_rollout_metrics
-        dev = self.device
-
-        def launch():
-            stream = torch.cuda.current_stream(dev).cuda_stream
-            rc = fn(*args, ctypes.c_void_p(stream))
-            if rc != 0:
-                _native.check(rc, "zmpc_rollout_metrics")
-        launch.metrics, launch.status, launch.inputs = out, status, keep
-        return launch
+        return self._launcher("zmpc_rollout_metrics", args, metrics=out, status=status,
+                              inputs=keep)
 
     def rollout_metrics(self, zmax, zmin, x0, kick=None, kick_step=-1, lengths=None, out=None,
                         status=None, fused_only=False):
@@ -472,9 +424,7 @@ class Plan:
         a temporary); fused_only=True raises NativeError there."""
         out, status, args, keep = self._rollout_metrics_args(zmax, zmin, x0, kick, kick_step,
                                                              lengths, out, status)
-        with torch.cuda.device(self.device):
-            stream = torch.cuda.current_stream(self.device).cuda_stream
-            rc = _native.load().zmpc_rollout_metrics(*args, ctypes.c_void_p(stream))
+        rc = _native.call("zmpc_rollout_metrics", self.device, *args, raises=False)
         if rc == _native.ZMPC_ESTATE and not fused_only:
             zmax_t, zmin_t, x0_t, kick_t, _, len_t = keep
             hist, status = self.rollout(zmax_t, zmin_t, x0_t, kick=kick_t, kick_step=kick_step,
@@ -493,10 +443,7 @@ class Plan:
         None: y-velocity impulse at kick_step.  params: controllers.herdt.HerdtParams.
         push: an analysis.Push instead of the kick (zmpc_herdt_rollout_pushed), with mass in kg.
         """
-        x0 = self._as_dev(x0)
-        if x0.dim() != 3 or x0.shape[1:] != (2, 3):
-            raise ValueError(f"x0 must be [B, 2, 3], got {tuple(x0.shape)}")
-        B = int(x0.shape[0])
+        x0, B = self._x0(x0)
         v = self._as_dev(v_ref)
         if v.dim() not in (2, 3) or v.shape[-1] != 2:
             raise ValueError(f"v_ref must be [B, n, 2] or [n, 2], got {tuple(v.shape)}")
@@ -507,7 +454,7 @@ class Plan:
             vs = 2 * n
         else:
             raise ValueError(f"v_ref must be [B, n, 2] or [n, 2], got {tuple(v.shape)}")
-        dev = self._dev()
+        dev = self._device
         st = torch.as_tensor(np.asarray(states, dtype=np.int8) if not isinstance(
             states, torch.Tensor) else states, dtype=torch.int8, device=dev).contiguous()
         nb = torch.as_tensor(np.asarray(nb_next, dtype=np.int32) if not isinstance(
@@ -525,25 +472,13 @@ class Plan:
         foot = torch.empty((B, n, 2), dtype=torch.float64, device=dev)
         status = torch.empty(B, dtype=torch.int32, device=dev)
         if push is not None:
-            if kick is not None:
-                raise ValueError("give either kick or push, not both")
-            c, keep = self._push_struct(push, mass, B)
-            with torch.cuda.device(self.device):
-                stream = torch.cuda.current_stream(self.device).cuda_stream
-                rc = _native.load().zmpc_herdt_rollout_pushed(
-                    self._live(), ctypes.byref(params), B, n, _ptr(v), vs, _ptr(st), ss, _ptr(nb),
-                    ns, _ptr(x0), ctypes.byref(c), _ptr(hist), _ptr(foot), _ptr(status),
-                    ctypes.c_void_p(stream))
-            del keep
-            _native.check(rc, "zmpc_herdt_rollout_pushed")
-            return hist, foot, status
-        with torch.cuda.device(self.device):
-            stream = torch.cuda.current_stream(self.device).cuda_stream
-            rc = _native.load().zmpc_herdt_rollout(
-                self._live(), ctypes.byref(params), B, n, _ptr(v), vs, _ptr(st), ss, _ptr(nb), ns,
-                _ptr(x0), _ptr(kick_t), int(kick_step), _ptr(hist), _ptr(foot), _ptr(status),
-                ctypes.c_void_p(stream))
-        _native.check(rc, "zmpc_herdt_rollout")
+            c, keep = self._push_struct(push, mass, B, kick)  # (keep: alive until the call is out)
+            name, disturbance = "zmpc_herdt_rollout_pushed", (ctypes.byref(c),)
+        else:
+            name, disturbance = "zmpc_herdt_rollout", (_ptr(kick_t), int(kick_step))
+        _native.call(name, self.device, self._live(), ctypes.byref(params), B, n, _ptr(v), vs,
+                     _ptr(st), ss, _ptr(nb), ns, _ptr(x0), *disturbance, _ptr(hist), _ptr(foot),
+                     _ptr(status))
         return hist, foot, status
 
     def herdt_step(self, params, x, v_win, s_win, current, foot, side):
@@ -552,7 +487,7 @@ class Plan:
         first footstep [B,2] (NaN: none), status [B])."""
         x = self._as_dev(x)
         B = int(x.shape[0])
-        dev = self._dev()
+        dev = self._device
         v = self._as_dev(v_win, (B, self.N, 2))
         f = self._as_dev(foot, (B, 2))
         i8 = lambda a, shape: torch.as_tensor(np.asarray(a, dtype=np.int8).reshape(shape),
@@ -561,12 +496,9 @@ class Plan:
         xn = torch.empty((B, 2, 3), dtype=torch.float64, device=dev)
         step = torch.empty((B, 2), dtype=torch.float64, device=dev)
         status = torch.empty(B, dtype=torch.int32, device=dev)
-        with torch.cuda.device(self.device):
-            stream = torch.cuda.current_stream(self.device).cuda_stream
-            rc = _native.load().zmpc_herdt_step(
-                self._live(), ctypes.byref(params), B, _ptr(x), _ptr(v), _ptr(sw), _ptr(cu), _ptr(f),
-                _ptr(sd), _ptr(xn), _ptr(step), _ptr(status), ctypes.c_void_p(stream))
-        _native.check(rc, "zmpc_herdt_step")
+        _native.call("zmpc_herdt_step", self.device, self._live(), ctypes.byref(params), B,
+                     _ptr(x), _ptr(v), _ptr(sw), _ptr(cu), _ptr(f), _ptr(sd), _ptr(xn), _ptr(step),
+                     _ptr(status))
         return xn, step, status
 
 

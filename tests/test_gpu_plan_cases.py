@@ -164,8 +164,9 @@ def test_export_refusals():
     lib = _native.load()
     N = 17
     case = (PC.case_name(N, 0), N, PC.POINTS[0])
-    sizes = {8: 4 * _native.kffa_rows(N), 9: _native.ksum_rows(N), 10: _native.SCAN_DOUBLES,
-             11: N * N, 12: N, 13: 2 * _native.FFT_PT, 14: 2 * _native.FFT_G_COMPLEX}
+    sizes = {what: count(N) for what, (_, count, _) in _native.EXPORTS.items() if what >= 8}
+    assert sorted(sizes) == list(range(8, 15)) and sizes[11] == N * N and sizes[12] == N
+    assert sizes[13] == 2 * _native.FFT_PT
     assert sizes[8] == 4 * ((N + 2) // 2 + 8) and sizes[9] == N + 18
     assert sizes[10] == PC.SCAN_DOUBLES and sizes[14] == 2 * PC.FFT_G_COMPLEX
     buf = np.full(max(sizes.values()) + 1, np.nan)
