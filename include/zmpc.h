@@ -505,6 +505,73 @@ int zmpc_herdt_rollout_pushed(const zmpc_plan* plan, const zmpc_herdt_params* pa
                               double* hist, double* foot, int32_t* status, void* stream);
 
 /*
+ * Per-walk survival metrics of a Herdt rollout, reduced on the device: did the footstep-adapting
+ * controller stay up?  zmpc_walk_metrics needs fixed CoP bounds; a Herdt walk has none, its
+ * support box follows the footsteps the QP chose.  Here the box is rebuilt from the rollout's own
+ * outputs.
+ *   hist [B, n, 2, 3], foot [B, n, 2] : what zmpc_herdt_rollout(_pushed) wrote
+ *   states [B, n] int8                : what it took (s_stride bytes between walks, 0 = shared)
+ *   foot_ref [B, n, 2] or NULL        : the feet of a nominal walk, normally the unpushed one
+ *                                       (foot_ref_stride doubles between walks, 0 = shared)
+ *   lengths [B] int64 or NULL         : live samples n_b per walk, clamped to [1, n] as in
+ *                                       zmpc_walk_metrics; rows from n_b on are never read
+ *   count_tol >= 0                    : the excursion above which a sample counts in viol_count
+ *   metrics [B, ZMPC_NHERDT_METRICS]
+ * The plan supplies h/g only (any plan kind); params supplies foot_length, foot_width,
+ * foot_spread, the facets and nfacets, and nothing else of it is read.
+ *
+ * The support of sample i, stated once.  Let j = max(i − 1, 0), f = foot[b, j], s = states[b, i].
+ *   - Row 0 of the QP built at step i − 1 belongs to the current foot of that step, so the
+ *     realised ZMP of sample i is held to a box round foot[i − 1], not foot[i]: at a landing
+ *     foot[i] has already jumped a step length.
+ *   - L_k: states[k] == SINGLE_SUPPORT, states[k+1] != SINGLE_SUPPORT and k + 1 < n_b — a landing
+ *     at step k; the rollout flips its side there and writes the new foot to row k + 1.
+ *   - side_j: the parity of the number of landings at steps k < j; 0 is left (the rollout's own
+ *     rule, :501-502).
+ *   - Sample 0 has no box: v_0 = 0.
+ *   - i >= 1, s != STANDING: the box is f ± ½(foot_length, foot_width) (:666, :680).
+ *   - i >= 1, s == STANDING: x as above; y is held to the hull of both feet, the other foot at
+ *     f_y − 2·foot_spread when side_j is left and f_y + 2·foot_spread when it is right, widened by
+ *     ½·foot_width on both sides (:716-734).  The reference drops a STANDING row from its QP while
+ *     walking rows remain in the window (:682-698); the metric still holds that sample to the
+ *     hull, since both feet are on the ground.
+ *   - v_i = max(z − hi, lo − z, 0) with z = c − (h/g)·c̈, uncontracted as in zmpc_walk_metrics.
+ * The QP is always feasible (its ZMP matrix is triangular with a non-zero diagonal and the jerk
+ * is unbounded): under any push the ZMP stays on or inside its box — it sits on the edge by
+ * design, so v is rounding noise and viol_count needs count_tol — while the CoM runs away.
+ * Whether the robot stayed up is told by dcm_dev_max, never by viol_max.
+ *
+ * Slot 2k + a holds quantity k of axis a (0: x, 1: y), over 0 <= i < n_b, with fs_i = foot[j]:
+ *   0 viol_max        max v_i
+ *   1 viol_argmax     the smallest i that attains it, −1 when viol_max is 0
+ *   2 viol_count      the number of samples with v_i > count_tol
+ *   3 com_dev_max     max |c_i − fs_i|
+ *   4 dcm_dev_max     max |c_i + ċ_i·sqrt(h/g) − fs_i|: the survival quantity
+ *   5 dcm_end         c + ċ·sqrt(h/g) − fs at i = n_b − 1, signed
+ *   6 step_shift_max  max |foot_i − foot_ref_i|: how far the controller stepped aside; 0 when
+ *                     foot_ref is NULL
+ * Slot 14, reach_slack_min: over the landings k, the minimum over the facets (a_x, a_y, b) of
+ * side_k's polytope of b − a·(foot[k+1] − foot[k]) (the sum a_x·d_x + a_y·d_y, uncontracted);
+ * +inf with no landing or no facets; zero: the step reached as far as it could.
+ * Slot 15, steps_landed: the number of landings.
+ * Non-finite rule, as zmpc_walk_metrics: a live sample i of axis a is non-finite when hist[b, i,
+ * a, :], foot[b, i, a] or (given) foot_ref[b, i, a] is not finite; such an axis reports viol_max
+ * = +inf, viol_argmax = the first such sample and NaN in its other slots, slot 14 is NaN if
+ * either axis is flagged, slot 15 and the other walks are unaffected.
+ * The reductions run in an order fixed by the lane numbers: two calls on the same input agree bit
+ * for bit.  No workspace, no status.  ZMPC_EINVAL before any device call: NULL plan or params;
+ * (B > 0) NULL hist, foot, states or metrics; B < 0; n < 1; count_tol negative or NaN; nfacets
+ * outside [0, 16]; a non-zero s_stride < n or foot_ref_stride < 2n.  B = 0 does nothing.
+ * Additive to ABI 7.
+ */
+#define ZMPC_NHERDT_METRICS 16
+int zmpc_herdt_walk_metrics(const zmpc_plan* plan, const zmpc_herdt_params* params, int64_t B,
+                            int64_t n, const double* hist, const double* foot,
+                            const int8_t* states, int64_t s_stride, const double* foot_ref,
+                            int64_t foot_ref_stride, const int64_t* lengths, double count_tol,
+                            double* metrics, void* stream);
+
+/*
  * Batched predict_herdt_joint (zmp_controller.py:533-826), one QP per instance, cold start:
  *   x [B, 2, 3] (x, y) states; v_win [B, N, 2] window of v_ref; s_win [B, N] window states;
  *   current [B] int8 current support state; foot [B, 2] current foot (x_fc, y_fc);

@@ -642,6 +642,34 @@ int zmpc_herdt_rollout_pushed(const zmpc_plan* P, const zmpc_herdt_params* prm, 
                             x0, nullptr, -1, push, hist, foot, status, stream);
 }
 
+int zmpc_herdt_walk_metrics(const zmpc_plan* P, const zmpc_herdt_params* prm, int64_t B,
+                            int64_t n, const double* hist, const double* foot,
+                            const int8_t* states, int64_t s_stride, const double* foot_ref,
+                            int64_t foot_ref_stride, const int64_t* lengths, double count_tol,
+                            double* metrics, void* stream) {
+  g_err.clear();
+  if (!P || !prm) return fail(ZMPC_EINVAL, "NULL plan or params");
+  if (B < 0 || n < 1) return fail(ZMPC_EINVAL, "need B >= 0 and n >= 1");
+  if (!(count_tol >= 0)) return fail(ZMPC_EINVAL, "need count_tol >= 0");
+  for (int sd = 0; sd < 2; ++sd)
+    if (prm->nfacets[sd] < 0 || prm->nfacets[sd] > ZMPC_HERDT_MAX_FACETS)
+      return fail(ZMPC_EINVAL, "polytope facets must be in [0, 16]");
+  if ((s_stride != 0 && s_stride < n) || (foot_ref_stride != 0 && foot_ref_stride < 2 * n))
+    return fail(ZMPC_EINVAL, "s_stride must be 0 (shared) or >= n, foot_ref_stride 0 or >= 2n");
+  if (B > 0 && (!hist || !foot || !states || !metrics))
+    return fail(ZMPC_EINVAL, "NULL array argument");
+  if (B > 0x7fffffff) return fail(ZMPC_EINVAL, "batch too large");
+  if (n > (1 << 24)) return fail(ZMPC_EINVAL, "walk too long");
+  if (B == 0) return ZMPC_OK;
+  DeviceGuard g(P->device);
+  if (g.err != hipSuccess) return hip_fail(g.err, "hipSetDevice");
+  hipError_t e = zmpc_launch_herdt_walk_metrics(P, prm, B, n, hist, foot, states, s_stride,
+                                                foot_ref, foot_ref_stride, lengths, count_tol,
+                                                metrics, (hipStream_t)stream);
+  if (e != hipSuccess) return hip_fail(e, "zmpc_herdt_walk_metrics launch");
+  return ZMPC_OK;
+}
+
 int zmpc_herdt_step(const zmpc_plan* P, const zmpc_herdt_params* prm, int64_t B,
                     const double* x, const double* v_win, const int8_t* s_win,
                     const int8_t* current, const double* foot, const int8_t* side,

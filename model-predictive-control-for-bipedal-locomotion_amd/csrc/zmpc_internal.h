@@ -162,6 +162,16 @@ hipError_t zmpc_launch_walk_metrics(const zmpc_plan* p, int64_t B, int64_t n, co
                                     const double* zmax, const double* zmin, int64_t bstride,
                                     const int64_t* lengths, double* metrics, hipStream_t s);
 
+// per-walk survival metrics of a Herdt rollout (herdt_metrics.hip): one wavefront per walk, reads
+// only p->hg and, of prm, the foot dimensions, the spread and the facets; foot_ref and lengths
+// may be NULL
+hipError_t zmpc_launch_herdt_walk_metrics(const zmpc_plan* p, const zmpc_herdt_params* prm,
+                                          int64_t B, int64_t n, const double* hist,
+                                          const double* foot, const int8_t* states,
+                                          int64_t sstride, const double* foot_ref,
+                                          int64_t rstride, const int64_t* lengths, double tol,
+                                          double* metrics, hipStream_t s);
+
 // The arguments of one zmpc_push_map / zmpc_push_map_shaped call (zmpc_push_map: duration 1, no
 // profile, the y axis).
 struct PushCall {

@@ -26,6 +26,7 @@ PLAN_STAGE_NAMES = ("prediction", "gram_PuTPu", "cholesky", "gain", "scan", "fft
                     "strict_lq_table", "total")
 HERDT_MAX_FACETS = 16  # include/zmpc.h ZMPC_HERDT_MAX_FACETS
 NMETRICS = 12    # include/zmpc.h ZMPC_NMETRICS
+NHERDT_METRICS = 16  # include/zmpc.h ZMPC_NHERDT_METRICS
 
 ZMPC_OK = 0
 ZMPC_EINVAL = -1
@@ -116,6 +117,9 @@ SIGNATURES = {
     "zmpc_herdt_rollout_pushed": (_C, [_P, _P, _L, _L, _P, _L, _P, _L, _P, _L, _P, _P, _P, _P,
                                        _P, _P]),
     "zmpc_herdt_step": (_C, [_P, _P, _L, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    # params, B, n, hist, foot, states, s_stride, foot_ref, foot_ref_stride, lengths, count_tol,
+    # metrics, stream
+    "zmpc_herdt_walk_metrics": (_C, [_P, _P, _L, _L, _P, _P, _P, _L, _P, _L, _P, _D, _P, _P]),
 }
 
 

@@ -23,6 +23,12 @@ A push that lasts several samples, with or without a force profile, has the resp
 ``Push`` describes the shove itself — force, direction, start step, duration, profile — for the
 pushed rollouts of every controller (``zmpc_rollout_pushed``, ``zmpc_herdt_rollout_pushed``;
 ``Plan.rollout(push=)``, the batch methods of ``ZMPController``).
+
+A Herdt walk has no fixed CoP bounds: ``zmpc_herdt_walk_metrics`` (``csrc/herdt_metrics.hip``)
+rebuilds the support box from the feet the QP chose and adds the divergent component of motion
+relative to the supporting foot, the quantity that tells whether the robot fell.
+``HerdtWalkMetrics`` names its sixteen numbers and ``herdt_walk_metrics_reference`` states them in
+NumPy (the checker, never a fallback).
 """
 
 import numpy as np
@@ -100,6 +106,139 @@ def walk_metrics_reference(hist, zmax, zmin, hg, lengths=None):
             out[b, 8 + a] = np.sqrt(np.mean((z - zr) ** 2))
             out[b, 10 + a] = c[-1] + cd[-1] * root - zr[-1]
     return out
+
+
+NHERDT_METRICS = 16  # include/zmpc.h ZMPC_NHERDT_METRICS
+# quantity k of axis a is slot 2k + a; slots 14 and 15 are per walk
+HERDT_SLOT_NAMES = ("viol_max", "viol_argmax", "viol_count", "com_dev_max", "dcm_dev_max",
+                    "dcm_end", "step_shift_max")
+HERDT_WALK_SLOTS = {"reach_slack_min": 14, "steps_landed": 15}
+
+
+class HerdtWalkMetrics:
+    """Named columns over a [B, 16] tensor or array of zmpc_herdt_walk_metrics; views, no copies.
+    [B, 2] (x, y) each, every one relative to the supporting foot fs_i = foot[max(i − 1, 0)]:
+
+    viol_max        largest excursion of the ZMP beyond the support box the QP held it to (the
+                    ZMP sits on the box edge by design: rounding noise, never the verdict)
+    viol_argmax     first sample that attains it (−1: none), as a float
+    viol_count      samples further out than count_tol
+    com_dev_max     largest distance of the CoM from the supporting foot
+    dcm_dev_max     largest distance of the divergent component of motion c + ċ·sqrt(h/g) from
+                    the supporting foot: the survival quantity
+    dcm_end         that component at the last sample, signed
+    step_shift_max  largest distance of a foot from the nominal walk's (0 without foot_ref)
+    and [B] each:
+    reach_slack_min smallest slack a landed step left on its swing polytope (+inf: no landing
+                    or no facets; 0: the step reached as far as it could)
+    steps_landed    landings
+    An axis that met a non-finite value reports viol_max = +inf, viol_argmax = the first such
+    sample and NaN elsewhere; reach_slack_min is then NaN."""
+
+    __slots__ = ("data",)
+
+    def __init__(self, data):
+        if data.ndim != 2 or data.shape[1] != NHERDT_METRICS:
+            raise ValueError(f"metrics must be [B, {NHERDT_METRICS}], got {tuple(data.shape)}")
+        self.data = data
+
+    def __getattr__(self, name):
+        if name in HERDT_WALK_SLOTS:
+            return self.data[:, HERDT_WALK_SLOTS[name]]
+        try:
+            k = HERDT_SLOT_NAMES.index(name)
+        except ValueError:
+            raise AttributeError(name) from None
+        return self.data[:, 2 * k:2 * k + 2]
+
+    def __len__(self):
+        return int(self.data.shape[0])
+
+    def __repr__(self):
+        return (f"HerdtWalkMetrics(B={len(self)}, slots={HERDT_SLOT_NAMES + tuple(HERDT_WALK_SLOTS)})")
+
+
+def herdt_walk_metrics_reference(hist, foot, states, hg, foot_length, foot_width, foot_spread,
+                                 facets=(None, None), lengths=None, foot_ref=None,
+                                 count_tol=1e-9):
+    """The statement of include/zmpc.h zmpc_herdt_walk_metrics in NumPy, walk by walk → [B, 16]:
+    the checker of the kernel, never a fallback.
+
+    hist [B, n, 2, 3]; foot [B, n, 2]; states [B, n] or a shared [n] int8 codes (0 STANDING,
+    2 SINGLE_SUPPORT); hg = h/g; facets: per side (left, right) an [F, 3] array of rows
+    (a_x, a_y, b) or None; lengths [B] or None; foot_ref [B, n, 2], a shared [n, 2] or None."""
+    hist = np.asarray(hist, np.float64)
+    foot = np.asarray(foot, np.float64)
+    states = np.asarray(states)
+    B, n = hist.shape[:2]
+    out = np.empty((B, NHERDT_METRICS))
+    root = np.sqrt(hg)
+    half = (0.5 * foot_length, 0.5 * foot_width)
+    fac = [np.zeros((0, 3)) if f is None else np.asarray(f, np.float64).reshape(-1, 3)
+           for f in facets]
+    for b in range(B):
+        nb = n if lengths is None else min(max(int(lengths[b]), 1), n)
+        st = (states if states.ndim == 1 else states[b])[:nb]
+        ft = foot[b, :nb]
+        ref = None if foot_ref is None else \
+            (np.asarray(foot_ref, np.float64) if np.ndim(foot_ref) == 2
+             else np.asarray(foot_ref[b], np.float64))[:nb]
+        j = np.maximum(np.arange(nb) - 1, 0)
+        fs = ft[j]                                                        # the supporting foot
+        # landing[k]: a landing at step k; side[i]: parity of the landings at steps < j_i
+        landing = np.zeros(nb, bool)
+        landing[:nb - 1] = (st[:-1] == 2) & (st[1:] != 2)
+        before = np.concatenate([[0], np.cumsum(landing)[:-1]])           # landings at steps < k
+        side = before[j] % 2
+        flagged = False
+        for a in range(2):
+            s = hist[b, :nb, a, :]
+            bad = ~(np.isfinite(s).all(axis=1) & np.isfinite(ft[:, a]))
+            if ref is not None:
+                bad |= ~np.isfinite(ref[:, a])
+            if bad.any():
+                flagged = True
+                out[b, a:14:2] = np.nan
+                out[b, a] = np.inf
+                out[b, 2 + a] = float(np.argmax(bad))
+                continue
+            c, cd, cdd = s[:, 0], s[:, 1], s[:, 2]
+            z = c - hg * cdd
+            lo, hi = fs[:, a] - half[a], fs[:, a] + half[a]
+            if a == 1:
+                other = np.where(side == 1, fs[:, 1] + 2.0 * foot_spread,
+                                 fs[:, 1] - 2.0 * foot_spread)
+                stand = st == 0
+                lo = np.where(stand, np.minimum(fs[:, 1], other) - half[1], lo)
+                hi = np.where(stand, np.maximum(fs[:, 1], other) + half[1], hi)
+            v = np.maximum(np.maximum(z - hi, lo - z), 0.0)
+            v[0] = 0.0                                                    # sample 0 has no box
+            vmax = v.max()
+            dcm = (c + cd * root) - fs[:, a]
+            out[b, a] = vmax
+            out[b, 2 + a] = float(np.argmax(v)) if vmax > 0 else -1.0
+            out[b, 4 + a] = float(np.count_nonzero(v > count_tol))
+            out[b, 6 + a] = np.abs(c - fs[:, a]).max()
+            out[b, 8 + a] = np.abs(dcm).max()
+            out[b, 10 + a] = dcm[-1]
+            out[b, 12 + a] = 0.0 if ref is None else np.abs(ft[:, a] - ref[:, a]).max()
+        slack = np.inf
+        for k in np.nonzero(landing)[0]:
+            f = fac[int(before[k] % 2)]
+            d = ft[k + 1] - ft[k]
+            if len(f):
+                slack = min(slack, float((f[:, 2] - (f[:, 0] * d[0] + f[:, 1] * d[1])).min()))
+        out[b, 14] = np.nan if flagged else slack
+        out[b, 15] = float(np.count_nonzero(landing))
+    return out
+
+
+def herdt_params_facets(params):
+    """The (left, right) facet arrays [F, 3] of a controllers.herdt.HerdtParams, as
+    herdt_walk_metrics_reference takes them."""
+    return tuple(np.array([[params.facets[sd][f][c] for c in range(3)]
+                           for f in range(params.nfacets[sd])], np.float64).reshape(-1, 3)
+                 for sd in range(2))
 
 
 def push_response(A, B, kx, C, dt, m, n):

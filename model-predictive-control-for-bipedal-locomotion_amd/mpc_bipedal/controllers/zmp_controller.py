@@ -18,7 +18,10 @@ the ZMP stay inside the support box, per walk, reduced on the device), ``critica
 unconstrained controller ``push_map`` / ``critical_force_exact`` (that push in closed form, at
 every step and in both directions, from one unpushed rollout).  The batch methods and
 ``critical_force`` also take a shove of any length, shape and planar direction
-(``push=analysis.Push(...)``; ``duration=``, ``profile=``) on every controller.
+(``push=analysis.Push(...)``; ``duration=``, ``profile=``) on every controller.  For the
+footstep-adapting controller the same two questions are ``herdt_walk_metrics`` (the support box
+rebuilt from the feet the QP chose, and the divergent component of motion as the verdict) and
+``critical_force_herdt``.
 """
 
 import warnings
@@ -27,8 +30,8 @@ from typing import Optional, Tuple
 import numpy as np
 import torch
 
-from ..analysis import (NMETRICS, Push, PushMap, WalkMetrics, check_profile, planar_push,
-                        unit_directions)
+from ..analysis import (NHERDT_METRICS, NMETRICS, HerdtWalkMetrics, Push, PushMap, WalkMetrics,
+                        check_profile, planar_push, unit_directions)
 from ..config import MPCConfig
 from ..models.lipm_model import lipm_matrices
 from ..solver import get_plan
@@ -249,16 +252,20 @@ class ZMPController:
             return hist[..., 0], hist, foot, status
         return hist[..., 0], hist, foot
 
-    def _herdt_rollout(self, x0, v_ref, st, kick, kick_step, check=True, push=None):
-        plan = self._plan()
+    def _herdt_host(self, plan, st):
+        """The host preparation of a Herdt rollout from the int8 states [B, n] or [n]: (params
+        sized by the most footsteps in a window of the padded states, nb_next shaped as st)."""
         N = plan.N
         st2 = np.atleast_2d(st)
         pad = np.concatenate([st2, np.repeat(st2[:, -1:], N, axis=1)], axis=1)
         n = st2.shape[1]
         prm = herdt.make_params(self.config, herdt.max_footsteps(pad, N, n))
         nb = np.array([[t[0] for t in herdt.find_nb_steps(p)][:n] for p in pad], np.int32)
-        if st.ndim == 1:
-            nb = nb[0]
+        return prm, (nb[0] if st.ndim == 1 else nb)
+
+    def _herdt_rollout(self, x0, v_ref, st, kick, kick_step, check=True, push=None):
+        plan = self._plan()
+        prm, nb = self._herdt_host(plan, st)
         hist, foot, status = plan.herdt_rollout(prm, v_ref, st, nb, x0, kick=kick,
                                                 kick_step=kick_step, push=push,
                                                 mass=self.config.m)
@@ -501,6 +508,143 @@ class ZMPController:
         lo = torch.zeros(B, **f64)
         hi = top.clone()
         never = ~passes(lo)
+        lo = torch.where(passes(top), top, lo)
+        for _ in range(int(iters)):
+            mid = 0.5 * (lo + hi)
+            ok = passes(mid)
+            lo, hi = torch.where(ok, mid, lo), torch.where(ok, hi, mid)
+        nan = torch.full_like(lo, float("nan"))
+        return torch.where(never, nan, lo), torch.where(never, nan, hi)
+
+    # ------------------------------------------------------------------ Herdt robustness
+    @staticmethod
+    def _herdt_states(state_ref):
+        """State enums, their names, int8 codes or a tensor of codes → int8 NumPy codes."""
+        if isinstance(state_ref, torch.Tensor):
+            return state_ref.cpu().numpy().astype(np.int8)
+        return herdt.encode_states(state_ref)
+
+    def herdt_walk_metrics(self, hist, foot, state_ref, foot_ref=None,
+                           walk_lengths=None) -> HerdtWalkMetrics:
+        """Did a Herdt walk stay up (addition; zmpc_herdt_walk_metrics)?  The support box of a
+        Herdt walk follows the footsteps its QP chose, so it is rebuilt from the walk's own feet:
+        sample i against the box round foot[i − 1], reduced on the device.
+
+        hist [B,n,2,3], foot [B,n,2]: generate_com_trajectory_herdt_batch's outputs (NumPy arrays
+        are staged to the device); state_ref [B,n] or a shared [n], as that method took it;
+        foot_ref [B,n,2] or [n,2]: the feet of the unpushed walk, for step_shift_max;
+        walk_lengths [B] live samples.  Returns analysis.HerdtWalkMetrics over one [B,16] device
+        tensor.  The QP is always feasible, so viol_max stays at rounding noise under any push:
+        read dcm_dev_max to see whether the robot fell."""
+        plan = self._plan()
+        dev = torch.device("cuda", plan.device)
+        h = torch.as_tensor(hist, dtype=torch.float64, device=dev).contiguous()
+        f = torch.as_tensor(foot, dtype=torch.float64, device=dev).contiguous()
+        prm = herdt.make_params(self.config, 0)
+        return HerdtWalkMetrics(plan.herdt_walk_metrics(
+            prm, h, f, self._herdt_states(state_ref), lengths=walk_lengths, foot_ref=foot_ref))
+
+    def critical_force_herdt(self, v_ref, state_ref, max_dcm_dev, x_init=None, force_step=None,
+                             direction=+1, F_hi: float = 1000.0, iters: int = 30,
+                             max_violation: float = 1e-9, max_com_dev: Optional[float] = None,
+                             duration: int = 1, profile=None):
+        """Largest shove each scenario of the footstep-adapting controller survives (addition):
+        critical_force for Herdt walks, with its bisection, bracket and NaN conventions.
+
+        B scenarios — from x_init [B,2,3], per-walk v_ref [B,n,2] or state_ref [B,n], or a [B]
+        force_step or direction.  Scenario b is pushed from history step force_step[b] on
+        (default n//2) for `duration` samples with force F·profile[j] (None: constant), by
+        direction[b]·F newtons on the y axis, or along planar vectors (dx, dy) given as a
+        two-dimensional [1, 2] or [B, 2] array.  A push passes when the solver reported nothing
+        (status == 0) and, on both axes, viol_max <= max_violation, dcm_dev_max <= max_dcm_dev
+        and, where set, com_dev_max <= max_com_dev.
+
+        max_dcm_dev has no default, because it is the verdict: the joint QP is always feasible
+        (the jerk is unbounded), so under any push the ZMP stays on its box edge and viol_max at
+        rounding noise while the CoM runs away.  The divergent component of motion relative to
+        the supporting foot tells: it stays within a step length on a walk that recovers and grows
+        exponentially on one that does not, so any bound of a step length or so (1 m, say) gives
+        nearly the same force.
+
+        The host preparation (padded states, nb_next, max_footsteps) is done once.  Each of the
+        iters + 2 evaluations is one zmpc_herdt_rollout_pushed into reused buffers, its [B, C]
+        amplitudes scaled on the device, and one zmpc_herdt_walk_metrics launch; nothing is
+        copied to the host inside the loop.  The unpushed evaluation comes first and its feet are
+        the foot_ref of the later ones.
+
+        Returns (F_lo, F_hi), [B] device tensors: F_lo passes, F_hi fails, F_hi − F_lo =
+        F_hi/2**iters; NaN in both where the walk fails unpushed; F_lo = F_hi = the search limit
+        where it passes even there.  Bisection assumes that pass/fail is monotone in F.  That is
+        an assumption here, as for strict plans in critical_force: the controller is piecewise
+        linear; on the walks of the tests the passing set was one interval."""
+        D, w = check_profile(duration, profile)
+        if max_dcm_dev is None or not (float(max_dcm_dev) > 0):
+            raise ValueError("max_dcm_dev must be a positive bound in metres: the ZMP of a Herdt "
+                             "walk never tells whether the robot fell, the DCM does")
+        if not (F_hi > 0) or iters < 0:
+            raise ValueError("need F_hi > 0 and iters >= 0")
+        planar = np.ndim(direction) == 2
+        unit = unit_directions(direction) if planar else None
+        plan = self._plan()
+        dev = torch.device("cuda", plan.device)
+        f64 = dict(dtype=torch.float64, device=dev)
+        v = torch.as_tensor(v_ref, **f64).contiguous()
+        n = int(v.shape[-2])
+        st = self._herdt_states(state_ref)
+        sized = (force_step, _direction_size(direction, unit))
+        sizes = [int(np.shape(a)[0]) for a in sized if a is not None and np.ndim(a) == 1]
+        if x_init is not None:
+            B = int(np.shape(x_init)[0])
+        elif v.dim() == 3:
+            B = int(v.shape[0])
+        elif st.ndim == 2:
+            B = int(st.shape[0])
+        else:
+            B = sizes[0] if sizes else 1
+        if any(s != B for s in sizes):
+            raise ValueError(f"force_step and direction must be scalars or [B] = [{B}] (planar "
+                             "directions [1, 2] or [B, 2])")
+        x0 = torch.zeros((B, 2, 3), **f64) if x_init is None else torch.as_tensor(x_init, **f64)
+        if force_step is None:
+            step = n // 2
+        elif np.ndim(force_step) == 0:
+            step = int(force_step)
+        else:
+            step = np.asarray(torch.as_tensor(force_step).cpu(), np.int64)
+        # one newton along each scenario's direction; the bisection scales the amplitudes
+        if planar:
+            d1, F1 = np.broadcast_to(unit, (B, 2)), np.ones(B)
+        else:
+            sign = np.sign(np.broadcast_to(np.asarray(direction, np.float64), (B,)))
+            d1 = np.stack([np.zeros(B), np.where(sign == 0, 1.0, sign)], axis=1)
+            F1 = np.abs(sign)  # (sign 0: no push, through a zero force)
+        prm, nb = self._herdt_host(plan, st)
+        launch = plan.herdt_rollout_launcher(prm, v, st, nb, x0,
+                                             Push(F1, d1, step, duration=D, profile=w),
+                                             self.config.m)
+        amp1 = launch.push_amp.clone()  # [B, C] for 1 N
+        metrics = torch.empty((B, NHERDT_METRICS), **f64)
+        foot_ref = torch.empty_like(launch.foot)
+        measure0, measure = (plan.herdt_walk_metrics_launcher(
+            prm, launch.hist, launch.foot, launch.states, foot_ref=ref,
+            count_tol=max_violation, out=metrics) for ref in (None, foot_ref))
+        m = HerdtWalkMetrics(metrics)
+
+        def passes(F, first=False):
+            launch.push_amp.copy_(amp1 * F[:, None])
+            launch()
+            (measure0 if first else measure)()
+            ok = (m.viol_max <= max_violation).all(dim=1)  # (+inf and NaN fail)
+            ok &= (m.dcm_dev_max <= max_dcm_dev).all(dim=1)
+            if max_com_dev is not None:
+                ok &= (m.com_dev_max <= max_com_dev).all(dim=1)
+            return ok & (launch.status == 0)
+
+        top = torch.full((B,), float(F_hi), **f64)
+        lo = torch.zeros(B, **f64)
+        hi = top.clone()
+        never = ~passes(lo, first=True)
+        foot_ref.copy_(launch.foot)
         lo = torch.where(passes(top), top, lo)
         for _ in range(int(iters)):
             mid = 0.5 * (lo + hi)

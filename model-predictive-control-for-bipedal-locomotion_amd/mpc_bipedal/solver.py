@@ -434,15 +434,11 @@ class Plan:
         return out, status
 
     # -- Herdt joint footstep QP (zmpc_herdt_rollout / zmpc_herdt_step) --------------------
-    def herdt_rollout(self, params, v_ref, states, nb_next, x0, kick=None, kick_step=-1,
-                      push=None, mass=None):
-        """Batched generate_com_trajectory_herdt → (hist [B,n,2,3], foot [B,n,2], status [B]).
-
-        v_ref [B,n,2] or a shared [n,2]; states [B,n] or [n] int8 codes; nb_next [B,n] or [n]
-        int32 (find_nb_steps of the padded states, first element); x0 [B,2,3]; kick [B] or
-        None: y-velocity impulse at kick_step.  params: controllers.herdt.HerdtParams.
-        push: an analysis.Push instead of the kick (zmpc_herdt_rollout_pushed), with mass in kg.
-        """
+    def _herdt_rollout_args(self, params, v_ref, states, nb_next, x0, kick, kick_step, push, mass,
+                            hist=None, foot=None, status=None):
+        """The checked arguments of one Herdt rollout → (hist, foot, status, (symbol, its
+        arguments without the stream, what they point to)); hist, foot, status: tensors to write
+        into, or None for new ones."""
         x0, B = self._x0(x0)
         v = self._as_dev(v_ref)
         if v.dim() not in (2, 3) or v.shape[-1] != 2:
@@ -454,32 +450,121 @@ class Plan:
             vs = 2 * n
         else:
             raise ValueError(f"v_ref must be [B, n, 2] or [n, 2], got {tuple(v.shape)}")
-        dev = self._device
-        st = torch.as_tensor(np.asarray(states, dtype=np.int8) if not isinstance(
-            states, torch.Tensor) else states, dtype=torch.int8, device=dev).contiguous()
-        nb = torch.as_tensor(np.asarray(nb_next, dtype=np.int32) if not isinstance(
-            nb_next, torch.Tensor) else nb_next, dtype=torch.int32, device=dev).contiguous()
         # per-walk [B, n] or shared [n]: a 2-D array must carry one row per walk (the kernel
         # reads row b of walk b)
-        for name, t in (("states", st), ("nb_next", nb)):
-            if t.dim() not in (1, 2) or t.shape[-1] != n or (t.dim() == 2 and t.shape[0] != B):
-                raise ValueError(f"{name} must be [B, n] = [{B}, {n}] or [n], got "
-                                 f"{tuple(t.shape)}")
-        ss = 0 if st.dim() == 1 else n
+        st, ss = self._states(states, B, n)
+        nb = torch.as_tensor(np.asarray(nb_next, dtype=np.int32) if not isinstance(
+            nb_next, torch.Tensor) else nb_next, dtype=torch.int32,
+            device=self._device).contiguous()
+        if tuple(nb.shape) not in ((n,), (B, n)):
+            raise ValueError(f"nb_next must be [B, n] = [{B}, {n}] or [n], got {tuple(nb.shape)}")
         ns = 0 if nb.dim() == 1 else n
         kick_t = None if kick is None else self._as_dev(kick, (B,))
-        hist = torch.empty((B, n, 2, 3), dtype=torch.float64, device=dev)
-        foot = torch.empty((B, n, 2), dtype=torch.float64, device=dev)
-        status = torch.empty(B, dtype=torch.int32, device=dev)
+        hist = self._out(hist, (B, n, 2, 3), torch.float64, _HIST_MSG)
+        foot = self._out(foot, (B, n, 2), torch.float64,
+                         "foot must be a contiguous float64 [B, n, 2] tensor on the plan's device")
+        status = self._out(status, (B,), torch.int32,
+                           "status must be a contiguous int32 [B] tensor on the plan's device")
         if push is not None:
-            c, keep = self._push_struct(push, mass, B, kick)  # (keep: alive until the call is out)
-            name, disturbance = "zmpc_herdt_rollout_pushed", (ctypes.byref(c),)
+            c, keep = self._push_struct(push, mass, B, kick)
+            # (the arguments hold the struct's address: it lives in what the caller keeps)
+            name, disturbance = "zmpc_herdt_rollout_pushed", (ctypes.addressof(c),)
         else:
+            c, keep = None, ()
             name, disturbance = "zmpc_herdt_rollout", (_ptr(kick_t), int(kick_step))
-        _native.call(name, self.device, self._live(), ctypes.byref(params), B, n, _ptr(v), vs,
-                     _ptr(st), ss, _ptr(nb), ns, _ptr(x0), *disturbance, _ptr(hist), _ptr(foot),
-                     _ptr(status))
+        args = (self._live(), ctypes.addressof(params), B, n, _ptr(v), vs, _ptr(st), ss, _ptr(nb),
+                ns, _ptr(x0), *disturbance, _ptr(hist), _ptr(foot), _ptr(status))
+        return hist, foot, status, (name, args, (params, v, st, nb, x0, kick_t, c, keep))
+
+    def herdt_rollout(self, params, v_ref, states, nb_next, x0, kick=None, kick_step=-1,
+                      push=None, mass=None):
+        """Batched generate_com_trajectory_herdt → (hist [B,n,2,3], foot [B,n,2], status [B]).
+
+        v_ref [B,n,2] or a shared [n,2]; states [B,n] or [n] int8 codes; nb_next [B,n] or [n]
+        int32 (find_nb_steps of the padded states, first element); x0 [B,2,3]; kick [B] or
+        None: y-velocity impulse at kick_step.  params: controllers.herdt.HerdtParams.
+        push: an analysis.Push instead of the kick (zmpc_herdt_rollout_pushed), with mass in kg.
+        """
+        hist, foot, status, (name, args, _) = self._herdt_rollout_args(
+            params, v_ref, states, nb_next, x0, kick, kick_step, push, mass)
+        _native.call(name, self.device, *args)
         return hist, foot, status
+
+    def herdt_rollout_launcher(self, params, v_ref, states, nb_next, x0, push, mass, hist=None,
+                               foot=None, status=None):
+        """rollout_launcher's counterpart for pushed Herdt walks: validate once and return a
+        zero-argument callable that re-issues zmpc_herdt_rollout_pushed on the current stream.
+        launch.hist, launch.foot, launch.status are its outputs, launch.states the int8 states on
+        the device and launch.push_amp the [B, C] amplitude tensor the launch reads (write new
+        amplitudes into it between launches, as critical_force_herdt does)."""
+        hist, foot, status, (name, args, keep) = self._herdt_rollout_args(
+            params, v_ref, states, nb_next, x0, None, -1, push, mass, hist, foot, status)
+        return self._launcher(name, args, hist=hist, foot=foot, status=status, inputs=keep,
+                              states=keep[2], push_amp=keep[-1][0])
+
+    def _states(self, states, B, n):
+        """Support states on the device → (int8 tensor, stride in bytes between walks): [B, n]
+        per walk (stride n) or a shared [n] (stride 0)."""
+        st = torch.as_tensor(np.asarray(states, dtype=np.int8) if not isinstance(
+            states, torch.Tensor) else states, dtype=torch.int8, device=self._device).contiguous()
+        if tuple(st.shape) not in ((n,), (B, n)):
+            raise ValueError(f"states must be [B, n] = [{B}, {n}] or [n], got {tuple(st.shape)}")
+        return st, (0 if st.dim() == 1 else n)
+
+    def _herdt_walk_metrics_args(self, params, hist, foot, states, lengths, foot_ref, count_tol,
+                                 out):
+        """The checked arguments of zmpc_herdt_walk_metrics → (out, its arguments without the
+        stream, what they point to)."""
+        B, n = self._hist_dims(hist)
+        nm = _native.NHERDT_METRICS
+        if not isinstance(foot, torch.Tensor) or tuple(foot.shape) != (B, n, 2) \
+                or foot.dtype != torch.float64 or foot.device != self._device \
+                or not foot.is_contiguous():
+            raise ValueError(f"foot must be a contiguous float64 [B, n, 2] = [{B}, {n}, 2] tensor "
+                             "on the plan's device")
+        st, ss = self._states(states, B, n)
+        ref, rs = None, 0
+        if foot_ref is not None:
+            ref = self._as_dev(foot_ref)
+            if tuple(ref.shape) not in ((n, 2), (B, n, 2)):
+                raise ValueError(f"foot_ref must be [B, n, 2] = [{B}, {n}, 2] or [n, 2], got "
+                                 f"{tuple(ref.shape)}")
+            rs = 0 if ref.dim() == 2 else 2 * n
+        len_t = self._index(lengths, B, "lengths")
+        out = self._out(out, (B, nm), torch.float64,
+                        f"out must be a contiguous float64 [B, {nm}] tensor on the plan's device")
+        args = (self._live(), ctypes.addressof(params), B, n, _ptr(hist), _ptr(foot), _ptr(st), ss,
+                _ptr(ref), rs, _ptr(len_t), float(count_tol), _ptr(out))
+        return out, args, (params, hist, foot, st, ref, len_t)
+
+    def herdt_walk_metrics(self, params, hist, foot, states, lengths=None, foot_ref=None,
+                           count_tol=1e-9, out=None):
+        """Per-walk survival metrics of a Herdt rollout (zmpc_herdt_walk_metrics, include/zmpc.h)
+        → [B, 16] device tensor (analysis.HerdtWalkMetrics names the slots).
+
+        params: controllers.herdt.HerdtParams (the foot dimensions, the spread and the facets are
+        read); hist [B, n, 2, 3] and foot [B, n, 2]: herdt_rollout's outputs, contiguous float64
+        tensors on the plan's device, never copied; states [B, n] or a shared [n] int8 codes, as
+        the rollout took them; lengths [B] live samples or None; foot_ref [B, n, 2] or a shared
+        [n, 2]: the feet of the nominal (unpushed) walk, or None; count_tol: the excursion above
+        which a sample counts in viol_count; out: a contiguous float64 [B, 16] tensor on the
+        plan's device to write into.  Asynchronous on the current stream; only h/g of the plan is
+        read."""
+        out, args, _ = self._herdt_walk_metrics_args(params, hist, foot, states, lengths, foot_ref,
+                                                     count_tol, out)
+        _native.call("zmpc_herdt_walk_metrics", self.device, *args)
+        return out
+
+    def herdt_walk_metrics_launcher(self, params, hist, foot, states, lengths=None, foot_ref=None,
+                                    count_tol=1e-9, out=None):
+        """Validate once and return a zero-argument callable that re-issues
+        zmpc_herdt_walk_metrics on the current stream (launch.metrics is its output): for
+        critical_force_herdt's loop and for timing.  The tensors must stay alive while the
+        launcher is used; a foot_ref tensor on the device is read at every launch, so it may be
+        filled after the launcher is made."""
+        out, args, keep = self._herdt_walk_metrics_args(params, hist, foot, states, lengths,
+                                                        foot_ref, count_tol, out)
+        return self._launcher("zmpc_herdt_walk_metrics", args, metrics=out, inputs=keep)
 
     def herdt_step(self, params, x, v_win, s_win, current, foot, side):
         """Batched predict_herdt_joint: x [B,2,3], v_win [B,N,2], s_win [B,N] int8,
