@@ -7,6 +7,7 @@ streams only) and launch the HIP kernels on torch's current stream.
 
 import ctypes
 import os
+import threading
 import weakref
 from collections import OrderedDict
 
@@ -20,6 +21,7 @@ from .models.lipm_model import plan_constants
 # (a plan holds N² matrices and the FFT tables; a caller sweeping horizons, as
 # run_compare_runtime.py:139 does, would otherwise keep one per N)
 _PLAN_CACHE = OrderedDict()
+_PLAN_CACHE_LOCK = threading.Lock()
 PLAN_CACHE_MAX = max(1, int(os.environ.get("ZMPC_PLAN_CACHE", "8")))
 
 # what Plan._out raises for a state history and for a metrics tensor
@@ -592,24 +594,29 @@ def get_plan(config, device=None) -> Plan:
     dev = _device_index(getattr(config, "backend", "hip")) if device is None else int(device)
     key = (dev, int(config.horizon), float(config.dt), float(config.h), float(config.g),
            float(config.Q), float(config.R), bool(config.strict))
-    p = _PLAN_CACHE.get(key)
-    if p is not None and p._h is not None:
-        _PLAN_CACHE.move_to_end(key)
+    # one lock over lookup, build and eviction: two threads that ask for the same configuration
+    # at once get the same plan (not one build each, the loser's freed under its caller), and
+    # the LRU bookkeeping never sees a key another thread has just evicted
+    with _PLAN_CACHE_LOCK:
+        p = _PLAN_CACHE.get(key)
+        if p is not None and p._h is not None:
+            _PLAN_CACHE.move_to_end(key)
+            return p
+        p = Plan(dev, key[1], key[2], key[3], key[4], key[5], key[6], key[7])
+        _PLAN_CACHE[key] = p
+        while len(_PLAN_CACHE) > PLAN_CACHE_MAX:
+            # drop the cache's reference only: a caller still holding the plan keeps it alive,
+            # the device memory is freed when the last reference goes (weakref finalizer)
+            _PLAN_CACHE.popitem(last=False)
         return p
-    p = Plan(dev, key[1], key[2], key[3], key[4], key[5], key[6], key[7])
-    _PLAN_CACHE[key] = p
-    while len(_PLAN_CACHE) > PLAN_CACHE_MAX:
-        # drop the cache's reference only: a caller still holding the plan keeps it alive,
-        # the device memory is freed when the last reference goes (weakref finalizer)
-        _PLAN_CACHE.popitem(last=False)
-    return p
 
 
 def clear_plan_cache(destroy: bool = False):
     """Empty get_plan's cache; with destroy=True also free every cached plan now (callers must
     not use those plans afterwards)."""
-    plans = list(_PLAN_CACHE.values())
-    _PLAN_CACHE.clear()
+    with _PLAN_CACHE_LOCK:
+        plans = list(_PLAN_CACHE.values())
+        _PLAN_CACHE.clear()
     if destroy:
         for p in plans:
             p.destroy()
