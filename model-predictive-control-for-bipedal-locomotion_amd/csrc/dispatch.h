@@ -390,6 +390,12 @@ constexpr int kStrictCholMaxN = 512;
 // by a static_assert).
 constexpr int ZMPC_STRICT_MAX_N = 2464;
 
+// Active-set pass cap of every strict kernel (strict.hip, strict_lq.hip, strict_scan.hip).  64 was
+// too few: at (Q, R, h) = (0.1, 1e-3, 0.5) and N = 400 the reference's exact answer takes 150
+// primal-dual passes from a cold start and 212 after an 800 N kick (strict_weights_long_ref.npz);
+// the cap only bounds a cycling iteration
+constexpr int kStrictMaxPasses = 1024;
+
 // horizons of the parallel-in-time kernel (strict_scan.hip): 32-lane instances to N = 512 (C ≤ 16
 // slots per lane: 256 VGPRs + 248 AGPRs), whole-wave ones to 960 (C ≤ 15: 256 + 236; C = 16 of 64
 // lanes spills 12 B to scratch)

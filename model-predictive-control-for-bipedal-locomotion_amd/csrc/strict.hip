@@ -22,9 +22,6 @@
 //   solve  each wave takes 4 instances: PDAS with the reduced Cholesky factor packed in LDS
 //          (lane-blocked 8×8 updates, LDS-only ordering), G/H row combinations as coalesced,
 //          4-row-deep pipelined loads; state advance, kick, history, next W.
-#include <cstdio>
-#include <cstdlib>
-
 #include "zmpc_internal.h"
 
 namespace {
@@ -34,7 +31,6 @@ typedef double dbl4 __attribute__((ext_vector_type(4)));
 constexpr int SNB = 16;            // instances per tile (= MFMA column tile)
 constexpr int SWAVES = 4;          // waves per workgroup
 constexpr int SPW = SNB / SWAVES;  // instances per wave
-constexpr int SMAXIT = 1024;       // PDAS iteration cap (as strict_lq.hip)
 
 struct StrictArgs {
   int N, Np, ld;         // horizon, padded to 16, W/D leading dimension
@@ -57,26 +53,7 @@ struct StrictArgs {
   int32_t* status;       // [B] or null
   double* scratch;       // per-wave factor scratch, sg_stride doubles each (gridDim*SWAVES slots)
   int64_t sg_stride;     // (N/2 + 1)²: the reduced system is min(|A|, |F|) <= N/2
-  unsigned long long* dbg;  // diagnostic phase counters (ZMPC_DEBUG_STRICT), null normally
-  int lds_chol;          // A/B: 1 = LDS Cholesky for every reduced size (ZMPC_STRICT_LDS_CHOL)
   int gsz;               // doubles of LDS holding G packed (0: G read from L2)
-};
-
-// Diagnostic phase timer: only when a.dbg is set (a separate, opt-in run; never in the bench).
-struct PhaseClock {
-  unsigned long long* dbg;
-  unsigned long long t;
-  __device__ explicit PhaseClock(unsigned long long* d)
-      : dbg(d), t(d ? __builtin_amdgcn_s_memtime() : 0) {}
-  __device__ void lap(int slot, int lane) {
-    if (!dbg) return;
-    const unsigned long long now = __builtin_amdgcn_s_memtime();
-    if (lane == 0) atomicAdd(dbg + slot, now - t);
-    t = now;
-  }
-  __device__ void count(int slot, unsigned long long v, int lane) {
-    if (dbg && lane == 0) atomicAdd(dbg + slot, v);
-  }
 };
 
 // Orders this wave's global and LDS accesses (waits for both counters).
@@ -375,28 +352,19 @@ __device__ __noinline__ bool reg_chol_solve(Gather gather, int m, double* rhs, d
 template <class Gather>
 __device__ __forceinline__ bool reduced_solve(const StrictArgs& a, const WaveWork& w, int m, Gather gather,
                               int lane) {
-  PhaseClock clk(a.dbg);
-  clk.count(12, m, lane);
-  clk.count(m <= 16 ? 16 : m <= 32 ? 17 : m <= 48 ? 18 : m <= 64 ? 19 : 20, 1, lane);
-  if (m <= 64 && m * (m + 1) / 2 <= a.pcap && !a.lds_chol) {
-    const bool ok = m <= 16   ? reg_chol_solve<16>(gather, m, w.nuc, w.S, lane)
-                    : m <= 32 ? reg_chol_solve<32>(gather, m, w.nuc, w.S, lane)
-                    : m <= 48 ? reg_chol_solve<48>(gather, m, w.nuc, w.S, lane)
-                              : reg_chol_solve<64>(gather, m, w.nuc, w.S, lane);
-    clk.lap(3, lane);
-    return ok;
+  if (m <= 64 && m * (m + 1) / 2 <= a.pcap) {
+    return m <= 16   ? reg_chol_solve<16>(gather, m, w.nuc, w.S, lane)
+           : m <= 32 ? reg_chol_solve<32>(gather, m, w.nuc, w.S, lane)
+           : m <= 48 ? reg_chol_solve<48>(gather, m, w.nuc, w.S, lane)
+                     : reg_chol_solve<64>(gather, m, w.nuc, w.S, lane);
   }
   if (m * (m + 1) / 2 <= a.pcap && m <= 128) {
     Tri<true> T{w.S, m};
     gather_packed(T, gather, lane);
     lds_sync();
-    clk.lap(2, lane);
     if (!wave_cholesky(T, lane)) return false;
-    clk.lap(3, lane);
     wave_chol_solve(T, w.nuc, lane);
-    clk.lap(4, lane);
   } else {
-    clk.count(14, 1, lane);
     Tri<false> T{w.Sg, m};
     for (int t = lane; t < m * m; t += 64) {
       const int r = t / m, c = t % m;
@@ -418,7 +386,6 @@ __device__ __forceinline__ double solve_instance(const StrictArgs& a, int64_t in
                                  const double* D, signed char* st, const WaveWork& w, int lane,
                                  int* flags) {
   const int N = a.N;
-  PhaseClock clk(a.dbg);
   double zs[NJ], hi[NJ], lo[NJ];  // D, z_max − c, z_min − c on the lane's slots
   {
     double bh[NJ], bl[NJ];
@@ -444,12 +411,9 @@ __device__ __forceinline__ double solve_instance(const StrictArgs& a, int64_t in
     }
   }
   lds_sync();
-  clk.lap(0, lane);
-  clk.count(11, 1, lane);
   const double tolz = 1e-13, tolnu = 1e-13;
   bool done = false;
-  for (int it = 0; it < SMAXIT; ++it) {
-    clk.count(9, 1, lane);
+  for (int it = 0; it < kStrictMaxPasses; ++it) {
     // compact the active and the free slots
     int m = 0, f = 0;
 #pragma unroll
@@ -465,9 +429,6 @@ __device__ __forceinline__ double solve_instance(const StrictArgs& a, int64_t in
       f += __popcll(bf);
     }
     lds_sync();
-    clk.lap(1, lane);
-    clk.count(10, m, lane);
-    if (m > f) clk.count(13, 1, lane);
     if (m == 0) {
 #pragma unroll
       for (int c = 0; c < NJ; ++c) {
@@ -559,7 +520,6 @@ __device__ __forceinline__ double solve_instance(const StrictArgs& a, int64_t in
       }
     }
     lds_sync();
-    clk.lap(5, lane);
     // primal-dual set update: release active slots with wrong-signed multipliers, activate
     // violated free slots
     signed char ns[NJ];
@@ -586,7 +546,6 @@ __device__ __forceinline__ double solve_instance(const StrictArgs& a, int64_t in
       }
     }
     changed = __any(changed);
-    clk.lap(6, lane);
     if (!changed) {
       done = true;
       break;
@@ -718,7 +677,6 @@ __global__ void __launch_bounds__(256) zmpc_strict_kernel(StrictArgs a) {
     __syncthreads();
 
     for (int64_t i = 0; i < nsteps; ++i) {
-      PhaseClock kclk(a.dbg);
       // ---- GEMM: D = G · W for the 16 instances of the tile (MFMA f64) ----------------
       dbl4 acc[NJ];
       tile_gemm<NJ>(a.G, a.N, Np, Wt, ld, wave, lane, acc);
@@ -733,7 +691,6 @@ __global__ void __launch_bounds__(256) zmpc_strict_kernel(StrictArgs a) {
         }
       }
       __syncthreads();
-      kclk.lap(7, lane);
 
       // ---- per-instance active set, state advance, next W ------------------------------
       for (int q = 0; q < SPW; ++q) {
@@ -776,9 +733,7 @@ __global__ void __launch_bounds__(256) zmpc_strict_kernel(StrictArgs a) {
         lds_sync();
         if (i + 1 < nsteps) build_w<NJ>(a, inst, i + 1, xn, Wt + s * ld, lane);
       }
-      kclk.lap(8, lane);
       __syncthreads();
-      kclk.lap(15, lane);
     }
     // ---- status: OR over the axes of a walk -------------------------------------------
     if (a.status != nullptr) {
@@ -909,7 +864,8 @@ __global__ void __launch_bounds__(64 * WWAVES) zmpc_strict_wave_kernel(StrictArg
   }
 }
 
-size_t wave_lds_bytes(int Np, int pcap, int gsz) {
+// (ld is the tile kernel's: the wave kernel's LDS has no W/D tile)
+size_t wave_lds_bytes(int Np, int /*ld*/, int pcap, int gsz) {
   return ((size_t)gsz + WWAVES * (6 * (size_t)Np + pcap + 4)) * sizeof(double) +
          (size_t)WWAVES * Np;
 }
@@ -920,57 +876,49 @@ size_t strict_lds_bytes(int Np, int ld, int pcap, int gsz) {
          SNB * Np;
 }
 
-}  // namespace
+// What differs between the launches of the tile and the wave kernel.
+struct CholKind {
+  void (*kernel[8])(StrictArgs);  // the instances NJ = ⌈N/64⌉ = 1..8
+  size_t (*lds_bytes)(int Np, int ld, int pcap, int gsz);
+  int waves;       // per workgroup
+  int ld_pad;      // W/D leading dimension − Np
+  bool tiles;      // grid: persistent over tiles of SNB instances, min(tiles, the plan's
+                   // strict_slots); else one workgroup per `waves` instances
+  bool pack_g;     // G packed in LDS when it fits beside a factor room for reduced systems of 32
+                   // (the tile kernel: measured slower at N = 150 — the factor room it leaves is
+                   // too small — so its G always streams from L2, gsz = 0)
+  const char* too_long;
+};
 
-hipError_t zmpc_strict_set_attrs() {
-  hipError_t e = hipSuccess;
-#define ZMPC_SATTR(J)                                                                   \
-  if (e == hipSuccess)                                                                  \
-    e = hipFuncSetAttribute((const void*)zmpc_strict_kernel<J>,                        \
-                            hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-  ZMPC_SATTR(1) ZMPC_SATTR(2) ZMPC_SATTR(3) ZMPC_SATTR(4) ZMPC_SATTR(5) ZMPC_SATTR(6)
-  ZMPC_SATTR(7) ZMPC_SATTR(8)
-#undef ZMPC_SATTR
-#define ZMPC_WATTR(J)                                                                   \
-  if (e == hipSuccess)                                                                  \
-    e = hipFuncSetAttribute((const void*)zmpc_strict_wave_kernel<J>,                   \
-                            hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-  ZMPC_WATTR(1) ZMPC_WATTR(2) ZMPC_WATTR(3) ZMPC_WATTR(4) ZMPC_WATTR(5) ZMPC_WATTR(6)
-  ZMPC_WATTR(7) ZMPC_WATTR(8)
-#undef ZMPC_WATTR
-  return e;
-}
+#define ZMPC_NJ8(K) {K<1>, K<2>, K<3>, K<4>, K<5>, K<6>, K<7>, K<8>}
+const CholKind kTileKind{ZMPC_NJ8(zmpc_strict_kernel), strict_lds_bytes, SWAVES, 4, true, false,
+                         "horizon too long for the strict solver's LDS tile (N="};
+const CholKind kWaveKind{ZMPC_NJ8(zmpc_strict_wave_kernel), wave_lds_bytes, WWAVES, 0, false, true,
+                         "horizon too long for the strict wave kernel's LDS (N="};
+#undef ZMPC_NJ8
 
-static hipError_t launch_strict(const zmpc_plan* p, StrictArgs a, hipStream_t s,
-                                std::string* why) {
+hipError_t launch_chol(const CholKind& k, const zmpc_plan* p, StrictArgs a, hipStream_t s,
+                       std::string* why) {
   if (p->N > kStrictCholMaxN) {
     *why = "strict solver supports horizon N <= 512";
     return hipErrorInvalidValue;
   }
   a.N = p->N;
   a.Np = (p->N + 15) & ~15;
-  a.ld = a.Np + 4;
+  a.ld = a.Np + k.ld_pad;
   const size_t budget = 160 * 1024 - 512;
-  if (strict_lds_bytes(a.Np, a.ld, 0, 0) > budget) {
-    *why = "horizon too long for the strict solver's LDS tile (N=" + std::to_string(p->N) + ")";
+  const int gsz = ((p->N * (p->N + 1) / 2) + 1) & ~1;
+  a.gsz = (k.pack_g && k.lds_bytes(a.Np, a.ld, 32 * 33 / 2, gsz) <= budget) ? gsz : 0;
+  const size_t fixed = k.lds_bytes(a.Np, a.ld, 0, a.gsz);
+  if (fixed > budget) {
+    *why = k.too_long + std::to_string(p->N) + ")";
     return hipErrorInvalidValue;
   }
-  // G packed in LDS when it fits beside a factor room for m <= 32 — N <= ~150; the rest of
-  // the room then holds the packed factor
-  // (A/B in the diagnostics build only: measured slower at N = 150 — the factor room it
-  // leaves is too small)
-#ifdef ZMPC_DIAG
-  static const bool lds_g = getenv("ZMPC_STRICT_LDS_G") != nullptr;
-#else
-  constexpr bool lds_g = false;
-#endif
-  const int gsz = ((p->N * (p->N + 1) / 2) + 1) & ~1;
-  a.gsz = (lds_g && strict_lds_bytes(a.Np, a.ld, 32 * 33 / 2, gsz) <= budget) ? gsz : 0;
-  // packed factor room for min(|A|, |F|) <= N/2 when it fits, else as much as fits
+  // packed factor room for min(|A|, |F|) <= N/2 when it fits, else as much as fits (larger
+  // reduced systems factor in the wave's global scratch)
   const int half = p->N / 2;
   int pcap = half * (half + 1) / 2;
-  const size_t fixed = strict_lds_bytes(a.Np, a.ld, 0, a.gsz);
-  const int fit = (int)((budget - fixed) / (SWAVES * sizeof(double)));
+  const int fit = (int)((budget - fixed) / (k.waves * sizeof(double)));
   if (pcap > fit) pcap = fit;
   a.pcap = pcap & ~1;
   a.Q = p->Q;
@@ -980,124 +928,41 @@ static hipError_t launch_strict(const zmpc_plan* p, StrictArgs a, hipStream_t s,
   a.Hz = p->Hz;
   // p(0) = T³/6·1 − T h/g  (zmp_controller.py:171 with i = j)
   a.p0 = p->T3_6 - p->Thg;
-  const int64_t ntiles = (a.ninst + SNB - 1) / SNB;
-  int grid = (int)std::min<int64_t>(ntiles, (int64_t)p->strict_slots);
+  const int64_t grid = k.tiles ? std::min<int64_t>((a.ninst + SNB - 1) / SNB, p->strict_slots)
+                               : (a.ninst + k.waves - 1) / k.waves;
   // the global factor room of the waves (reduced systems that fit neither registers nor the
   // packed LDS factor) is allocated per launch, stream-ordered, so concurrent launches of one
   // plan on different streams never share it; m = min(|A|, |F|) <= N/2 bounds its size
   const int64_t half1 = p->N / 2 + 1;
   a.sg_stride = half1 * half1;
-  const size_t sg_bytes = (size_t)grid * SWAVES * (size_t)a.sg_stride * sizeof(double);
+  const size_t sg_bytes = (size_t)grid * k.waves * (size_t)a.sg_stride * sizeof(double);
   if (hipMallocAsync((void**)&a.scratch, sg_bytes, s) != hipSuccess) {
     (void)hipGetLastError();
     return hipErrorOutOfMemory;
-  }
-  const size_t lds = strict_lds_bytes(a.Np, a.ld, a.pcap, a.gsz);
-#ifdef ZMPC_DIAG
-  static const bool lds_chol = getenv("ZMPC_STRICT_LDS_CHOL") != nullptr;  // A/B only
-  static const bool dbg_on = getenv("ZMPC_DEBUG_STRICT") != nullptr;       // diagnostics only
-#else
-  constexpr bool lds_chol = false, dbg_on = false;
-#endif
-  a.lds_chol = lds_chol ? 1 : 0;
-  static unsigned long long* dbgbuf = nullptr;
-  if (dbg_on && !dbgbuf) (void)hipMalloc((void**)&dbgbuf, 32 * sizeof(unsigned long long));
-  if (dbg_on && dbgbuf) {
-    (void)hipMemsetAsync(dbgbuf, 0, 32 * sizeof(unsigned long long), s);
-    a.dbg = dbgbuf;
   }
   const int nj = (a.N + 63) / 64;
-  switch (nj) {
-#define ZMPC_SCASE(J)                                                                        \
-  case J:                                                                                    \
-    hipLaunchKernelGGL(zmpc_strict_kernel<J>, dim3(grid), dim3(256), lds, s, a);             \
-    break;
-    ZMPC_SCASE(1) ZMPC_SCASE(2) ZMPC_SCASE(3) ZMPC_SCASE(4) ZMPC_SCASE(5) ZMPC_SCASE(6)
-    ZMPC_SCASE(7) ZMPC_SCASE(8)
-#undef ZMPC_SCASE
-    default:
-      (void)hipFreeAsync(a.scratch, s);
-      *why = "unsupported horizon";
-      return hipErrorInvalidValue;
-  }
-  hipError_t e = hipGetLastError();
-  const hipError_t ef = hipFreeAsync(a.scratch, s);
-  if (e == hipSuccess) e = ef;
-  if (dbg_on && dbgbuf && e == hipSuccess) {
-    unsigned long long h[32];
-    (void)hipStreamSynchronize(s);
-    (void)hipMemcpy(h, dbgbuf, sizeof(h), hipMemcpyDeviceToHost);
-    fprintf(stderr,
-            "[zmpc strict dbg] grid=%d pcap=%d cycles: prep=%llu compact=%llu gather=%llu "
-            "chol=%llu cholsolve=%llu branch=%llu setupd=%llu gemm=%llu inst_all=%llu "
-            "barrier=%llu | solves=%llu iters=%llu sum_m=%llu primal=%llu sum_fact=%llu "
-            "global_fact=%llu\n",
-            grid, a.pcap, h[0], h[1], h[2], h[3], h[4], h[5], h[6], h[7], h[8], h[15], h[11],
-            h[9], h[10], h[13], h[12], h[14]);
-    fprintf(stderr, "[zmpc strict dbg] reduced sizes: <=16 %llu, 17-32 %llu, 33-48 %llu, "
-            "49-64 %llu, >64 %llu; gsz=%d\n", h[16], h[17], h[18], h[19], h[20], a.gsz);
-  }
-  return e;
-}
-
-static hipError_t launch_strict_wave(const zmpc_plan* p, StrictArgs a, hipStream_t s,
-                                     std::string* why) {
-  if (p->N > kStrictCholMaxN) {
-    *why = "strict solver supports horizon N <= 512";
+  if (nj < 1 || nj > 8) {
+    (void)hipFreeAsync(a.scratch, s);
+    *why = "unsupported horizon";
     return hipErrorInvalidValue;
   }
-  a.N = p->N;
-  a.Np = (p->N + 15) & ~15;
-  a.ld = a.Np;
-  a.Q = p->Q;
-  a.hg = p->hg;
-  a.lc = p->lc;
-  a.G = p->G;
-  a.Hz = p->Hz;
-  a.p0 = p->T3_6 - p->Thg;  // p(0) (zmp_controller.py:171, i = j)
-  a.lds_chol = 0;
-  a.dbg = nullptr;
-  const size_t budget = 160 * 1024 - 512;
-  // G packed in LDS when it fits beside a factor room for reduced systems of 32
-  const int gsz = ((p->N * (p->N + 1) / 2) + 1) & ~1;
-  a.gsz = wave_lds_bytes(a.Np, 32 * 33 / 2, gsz) <= budget ? gsz : 0;
-  if (wave_lds_bytes(a.Np, 0, a.gsz) > budget) {
-    *why = "horizon too long for the strict wave kernel's LDS (N=" + std::to_string(p->N) + ")";
-    return hipErrorInvalidValue;
-  }
-  // packed factor room for min(|A|, |F|) <= N/2 when it fits, else as much as fits (larger
-  // reduced systems factor in the wave's global scratch)
-  const int half = p->N / 2;
-  int pcap = half * (half + 1) / 2;
-  const int fit = (int)((budget - wave_lds_bytes(a.Np, 0, a.gsz)) / (WWAVES * sizeof(double)));
-  if (pcap > fit) pcap = fit;
-  a.pcap = pcap & ~1;
-  const int64_t grid = (a.ninst + WWAVES - 1) / WWAVES;
-  const int64_t half1 = p->N / 2 + 1;
-  a.sg_stride = half1 * half1;
-  const size_t sg_bytes = (size_t)grid * WWAVES * (size_t)a.sg_stride * sizeof(double);
-  if (hipMallocAsync((void**)&a.scratch, sg_bytes, s) != hipSuccess) {
-    (void)hipGetLastError();
-    return hipErrorOutOfMemory;
-  }
-  const size_t lds = wave_lds_bytes(a.Np, a.pcap, a.gsz);
-  switch ((a.N + 63) / 64) {
-#define ZMPC_WCASE(J)                                                                       \
-  case J:                                                                                   \
-    hipLaunchKernelGGL(zmpc_strict_wave_kernel<J>, dim3((unsigned)grid), dim3(64 * WWAVES), \
-                       lds, s, a);                                                          \
-    break;
-    ZMPC_WCASE(1) ZMPC_WCASE(2) ZMPC_WCASE(3) ZMPC_WCASE(4) ZMPC_WCASE(5) ZMPC_WCASE(6)
-    ZMPC_WCASE(7) ZMPC_WCASE(8)
-#undef ZMPC_WCASE
-    default:
-      (void)hipFreeAsync(a.scratch, s);
-      *why = "unsupported horizon";
-      return hipErrorInvalidValue;
-  }
-  hipError_t e = hipGetLastError();
+  hipLaunchKernelGGL(k.kernel[nj - 1], dim3((unsigned)grid), dim3(64 * k.waves),
+                     k.lds_bytes(a.Np, a.ld, a.pcap, a.gsz), s, a);
+  const hipError_t e = hipGetLastError();
   const hipError_t ef = hipFreeAsync(a.scratch, s);
   return e != hipSuccess ? e : ef;
+}
+
+}  // namespace
+
+hipError_t zmpc_strict_set_attrs() {
+  hipError_t e = hipSuccess;
+  for (const CholKind* k : {&kTileKind, &kWaveKind})
+    for (auto kernel : k->kernel)
+      if (e == hipSuccess)
+        e = hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                160 * 1024);
+  return e;
 }
 
 // WAVE: the one-instance-per-wave kernel, else the tile kernel
@@ -1107,13 +972,6 @@ static hipError_t rollout_chol(const zmpc_plan* p, const RolloutCall& c, hipStre
   if (!p->G) {
     *why = "plan was created without strict workspace";
     return hipErrorInvalidValue;
-  }
-  if (c.n == 1) {
-    hipError_t e = hipMemcpyAsync(c.hist, c.x0, 6 * sizeof(double) * (size_t)c.B,
-                                  hipMemcpyDeviceToDevice, s);
-    if (e != hipSuccess) return e;
-    if (c.status) return hipMemsetAsync(c.status, 0, sizeof(int32_t) * c.B, s);
-    return hipSuccess;
   }
   if (c.status) {
     hipError_t e = hipMemsetAsync(c.status, 0, sizeof(int32_t) * c.B, s);
@@ -1132,7 +990,7 @@ static hipError_t rollout_chol(const zmpc_plan* p, const RolloutCall& c, hipStre
   a.kick_steps = c.kick_steps;
   a.out = c.hist;
   a.status = c.status;
-  return WAVE ? launch_strict_wave(p, a, s, why) : launch_strict(p, a, s, why);
+  return launch_chol(WAVE ? kWaveKind : kTileKind, p, a, s, why);
 }
 
 template <bool WAVE>
@@ -1153,7 +1011,7 @@ static hipError_t step_chol(const zmpc_plan* p, const StepCall& c, hipStream_t s
   a.kick_step = -1;
   a.out = c.x_next;
   a.status = c.status;
-  return WAVE ? launch_strict_wave(p, a, s, why) : launch_strict(p, a, s, why);
+  return launch_chol(WAVE ? kWaveKind : kTileKind, p, a, s, why);
 }
 
 hipError_t zmpc_launch_rollout_strict_tile(const zmpc_plan* p, const RolloutCall& c,

@@ -13,12 +13,19 @@ StrictKind kind_for(const zmpc_plan* p, int64_t ninst) {
 
 hipError_t zmpc_launch_rollout_strict(const zmpc_plan* p, const RolloutCall& c, hipStream_t s,
                                       std::string* why) {
-  const StrictKind kind = kind_for(p, 2 * c.B);  // an instance per walk and axis
-  if (kind == StrictKind::Scan && c.n > 1) return zmpc_launch_rollout_strict_scan(p, c, s, why);
-  if (kind == StrictKind::Lq && c.n > 1) return zmpc_launch_rollout_strict_lq(p, c, s, why);
-  // (n = 1, no QP solve, is the history copy of the reduced-Cholesky entry points)
-  return kind == StrictKind::Wave ? zmpc_launch_rollout_strict_wave(p, c, s, why)
-                                  : zmpc_launch_rollout_strict_tile(p, c, s, why);
+  if (c.n == 1) {  // no QP solve, whatever the solver: the history is the initial state
+    hipError_t e = hipMemcpyAsync(c.hist, c.x0, 6 * sizeof(double) * (size_t)c.B,
+                                  hipMemcpyDeviceToDevice, s);
+    if (e == hipSuccess && c.status) e = hipMemsetAsync(c.status, 0, sizeof(int32_t) * c.B, s);
+    return e;
+  }
+  switch (kind_for(p, 2 * c.B)) {  // an instance per walk and axis
+    case StrictKind::Scan: return zmpc_launch_rollout_strict_scan(p, c, s, why);
+    case StrictKind::Lq: return zmpc_launch_rollout_strict_lq(p, c, s, why);
+    case StrictKind::Wave: return zmpc_launch_rollout_strict_wave(p, c, s, why);
+    case StrictKind::Tile: break;
+  }
+  return zmpc_launch_rollout_strict_tile(p, c, s, why);
 }
 
 hipError_t zmpc_launch_step_strict(const zmpc_plan* p, const StepCall& c, hipStream_t s,

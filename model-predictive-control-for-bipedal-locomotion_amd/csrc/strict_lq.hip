@@ -58,10 +58,6 @@ namespace {
 
 using namespace zmpc_eta;
 
-// active-set pass cap (as strict.hip).  64 was too few: at (Q, R, h) = (0.1, 1e-3, 0.5) and
-// N = 400 the reference's exact answer takes 150 primal-dual passes from a cold start and 212
-// after an 800 N kick (strict_weights_long_ref.npz); the cap only bounds a cycling iteration
-constexpr int LQ_MAXIT = 1024;
 #ifdef ZMPC_DIAG
 constexpr bool kLqProf = true;  // per-phase clocks (ZMPC_LQ_PROF), diagnostics build only
 #else
@@ -599,75 +595,60 @@ __device__ __forceinline__ void seg_sweep_b(const LqArgs& a, int j, Ric& v, cons
   lap(6);
 }
 
-// Checkpoints are written once and read once per pass.  With per-walk bounds (whose rows are
-// re-read every timestep and do not fit the caches) they go non-temporal (NT), so they do not
-// push those rows out; with a shared CoP the bounds are cache-resident anyway and the
-// checkpoints are better off cached (config 3: 84.4 → 82.5 ms NT; config 4: 112.6 → 102.4 ms
-// cached, profiles/r3nt/).
-template <bool NT>
-struct CkIO {
-  __device__ __forceinline__ void st(double* p, double v) const {
-    if constexpr (NT)
-      __builtin_nontemporal_store(v, p);
-    else
-      *p = v;
-  }
-  __device__ __forceinline__ double ld(const double* p) const {
-    if constexpr (NT)
-      return __builtin_nontemporal_load(p);
-    else
-      return *p;
-  }
-};
-
+// Checkpoints are written once and read once per pass, with ordinary (cached) loads and stores:
+// non-temporal ones won only while per-walk bound rows competed for the caches (config 3 84.4 →
+// 82.5 ms, profiles/r3nt/) and lost once run-length bounds took those rows away (config 3 55.4
+// cached vs 56.7 ms, profiles/r5m/).
 constexpr int kCkStride = 9 * 64;  // doubles of one segment's checkpoint per 64 lanes
 
-template <bool NT>
-__device__ __forceinline__ void ck_store(const CkIO<NT>& io, double* ck, int j, const Ric& v,
+// An empty argument of the four helpers below, there for the compiler alone.  The kernel's task
+// lambda captures the kernel's one CkTag at each call, as it captured the policy object that stood
+// here; without that capture the run-length instances get another register allocation (one more
+// instruction each) and configs 3 and 4 ran 0.4–0.6 % slower (profiles/r11/strict_refactor/).
+struct CkTag {};
+
+__device__ __forceinline__ void ck_store(const CkTag&, double* ck, int j, const Ric& v,
                                          int lane) {
   double* p = ck + (size_t)j * kCkStride + lane;
-  io.st(p + 0, v.p00);
-  io.st(p + 64, v.p01);
-  io.st(p + 128, v.p02);
-  io.st(p + 192, v.p11);
-  io.st(p + 256, v.p12);
-  io.st(p + 320, v.p22);
-  io.st(p + 384, v.s0);
-  io.st(p + 448, v.s1);
-  io.st(p + 512, v.s2);
+  p[0] = v.p00;
+  p[64] = v.p01;
+  p[128] = v.p02;
+  p[192] = v.p11;
+  p[256] = v.p12;
+  p[320] = v.p22;
+  p[384] = v.s0;
+  p[448] = v.s1;
+  p[512] = v.s2;
 }
 
-template <bool NT>
-__device__ __forceinline__ void ck_store_s(const CkIO<NT>& io, double* ck, int j, const Ric& v,
+__device__ __forceinline__ void ck_store_s(const CkTag&, double* ck, int j, const Ric& v,
                                            int lane) {
   double* p = ck + (size_t)j * kCkStride + lane;
-  io.st(p + 384, v.s0);
-  io.st(p + 448, v.s1);
-  io.st(p + 512, v.s2);
+  p[384] = v.s0;
+  p[448] = v.s1;
+  p[512] = v.s2;
 }
 
-template <bool NT>
-__device__ __forceinline__ void ck_load(const CkIO<NT>& io, const double* ck, int j, Ric& v,
+__device__ __forceinline__ void ck_load(const CkTag&, const double* ck, int j, Ric& v,
                                         int lane) {
   const double* p = ck + (size_t)j * kCkStride + lane;
-  v.p00 = io.ld(p + 0);
-  v.p01 = io.ld(p + 64);
-  v.p02 = io.ld(p + 128);
-  v.p11 = io.ld(p + 192);
-  v.p12 = io.ld(p + 256);
-  v.p22 = io.ld(p + 320);
-  v.s0 = io.ld(p + 384);
-  v.s1 = io.ld(p + 448);
-  v.s2 = io.ld(p + 512);
+  v.p00 = p[0];
+  v.p01 = p[64];
+  v.p02 = p[128];
+  v.p11 = p[192];
+  v.p12 = p[256];
+  v.p22 = p[320];
+  v.s0 = p[384];
+  v.s1 = p[448];
+  v.s2 = p[512];
 }
 
-template <bool NT>
-__device__ __forceinline__ void ck_load_s(const CkIO<NT>& io, const double* ck, int j, Ric& v,
+__device__ __forceinline__ void ck_load_s(const CkTag&, const double* ck, int j, Ric& v,
                                           int lane) {
   const double* p = ck + (size_t)j * kCkStride + lane;
-  v.s0 = io.ld(p + 384);
-  v.s1 = io.ld(p + 448);
-  v.s2 = io.ld(p + 512);
+  v.s0 = p[384];
+  v.s1 = p[448];
+  v.s2 = p[512];
 }
 
 // G waves per workgroup.  G = 8: waves 0..3 take the x axis and 4..7 the y axis of the same
@@ -686,7 +667,7 @@ __device__ __forceinline__ void ck_load_s(const CkIO<NT>& io, const double* ck, 
 // PUSH: the instances of zmpc_rollout_pushed, whose time loop takes a push window (a.push) on
 // either axis; the others take the one-sample y kick as before, instruction for instruction (the
 // window in the kick's instances cost config 3 1.2 %).
-template <int S, int G, bool NT, bool RUNS, bool QUEUE, bool PUSH = false>
+template <int S, int G, bool RUNS, bool QUEUE, bool PUSH = false>
 __global__ void __launch_bounds__(64 * G, 2)
     zmpc_strict_lq_kernel(LqArgs a, const double* __restrict__ tab) {
   extern __shared__ __attribute__((aligned(16))) unsigned char lq_smem[];
@@ -710,7 +691,7 @@ __global__ void __launch_bounds__(64 * G, 2)
   // nearly all of its 129 GB per launch)
   double* ckl = xpark + 3 * 64;
   double* ck = a.ck + (size_t)gw * a.NS * kCkStride;
-  const CkIO<NT> io{};
+  const CkTag io{};  // (see CkTag)
   // work counters, wave-uniform 64-bit sums (scalar registers): wave passes, lane passes (the
   // lanes taking part) and their working-set slots
   unsigned long long n_wave_pass = 0, n_lane_pass = 0, n_ws_slots = 0;
@@ -1010,7 +991,7 @@ __global__ void __launch_bounds__(64 * G, 2)
         lap(7);
       }
       ++it;
-      if (changed && it >= LQ_MAXIT) {
+      if (changed && it >= kStrictMaxPasses) {
         fq |= ZMPC_ST_MAXITER;
         changed = false;
       }
@@ -1256,50 +1237,36 @@ hipError_t stage(const double* hi, const double* lo, int64_t sb, int64_t st, int
   return hipGetLastError();
 }
 
-// Workgroup shapes: G waves per workgroup (the G waves' slot flags must fit a CU's LDS), each
-// with cached or non-temporal checkpoints.
-struct LqVariant {
+// The instantiated kernels, one row each: G waves per workgroup (dispatch.h lq_shape: 8 by
+// default, 4 for N up to 2176, 2 up to ZMPC_STRICT_MAX_N; the G waves' slot flags must fit a CU's
+// LDS), bounds by runs or by rows, the task queue (G = 8 only), and the push window of
+// zmpc_rollout_pushed.  (The queue form exists for run-length bounds only: with the bounds staged
+// one row per sample, ZMPC_OPT_STRICT_BOUNDS = 1, its instances spill 20 B — those launches take
+// the one-round form.)
+using LqKernel = void (*)(LqArgs, const double*);
+
+struct LqInstance {
   int G;
-  void (*kernel)(LqArgs, const double*);     // checkpoints cached (shared CoP, window mode)
-  void (*kernel_nt)(LqArgs, const double*);  // checkpoints non-temporal (per-walk bounds)
-  void (*kernel_runs)(LqArgs, const double*);     // run-length bounds, cached checkpoints
-  void (*kernel_runs_nt)(LqArgs, const double*);  // run-length bounds, non-temporal
-  // the same four with the task queue (G = 8 only; null otherwise)
-  void (*q_kernel)(LqArgs, const double*);
-  void (*q_kernel_nt)(LqArgs, const double*);
-  void (*q_kernel_runs)(LqArgs, const double*);
-  void (*q_kernel_runs_nt)(LqArgs, const double*);
-  // the push-window instances (zmpc_rollout_pushed), cached checkpoints: bounds by rows, by runs,
-  // and by runs with the task queue (G = 8 only; null otherwise)
-  void (*p_kernel)(LqArgs, const double*);
-  void (*p_kernel_runs)(LqArgs, const double*);
-  void (*p_q_kernel_runs)(LqArgs, const double*);
+  bool runs, queue, push;
+  LqKernel kernel;
 };
 
-#define ZMPC_LQK(G, Q)                                                               \
-  zmpc_strict_lq_kernel<LQ_S, G, false, false, Q>, zmpc_strict_lq_kernel<LQ_S, G, true, false, Q>, \
-      zmpc_strict_lq_kernel<LQ_S, G, false, true, Q>, zmpc_strict_lq_kernel<LQ_S, G, true, true, Q>
-#define ZMPC_LQP(G) \
-  zmpc_strict_lq_kernel<LQ_S, G, false, false, false, true>, \
-      zmpc_strict_lq_kernel<LQ_S, G, false, true, false, true>
-#define ZMPC_LQV(G) {G, ZMPC_LQK(G, false), nullptr, nullptr, nullptr, nullptr, ZMPC_LQP(G), nullptr}
-// (The queue form exists for run-length bounds only: with the bounds staged one row per sample,
-// ZMPC_OPT_STRICT_BOUNDS = 1, its instances spill 20 B — those launches take the one-round form.)
-const LqVariant kLqVariants[] = {
-    {8, ZMPC_LQK(8, false), nullptr, nullptr, zmpc_strict_lq_kernel<LQ_S, 8, false, true, true>,
-     zmpc_strict_lq_kernel<LQ_S, 8, true, true, true>, ZMPC_LQP(8),
-     zmpc_strict_lq_kernel<LQ_S, 8, false, true, true, true>},  // default
-    ZMPC_LQV(4),  // N up to 2176 (the default G = 8: up to 896)
-    ZMPC_LQV(2),  // N up to 2464 (ZMPC_STRICT_MAX_N)
+#define ZMPC_LQI(G, R, Q, P) {G, R, Q, P, zmpc_strict_lq_kernel<LQ_S, G, R, Q, P>}
+const LqInstance kLqInstances[] = {
+    ZMPC_LQI(8, false, false, false), ZMPC_LQI(8, true, false, false),
+    ZMPC_LQI(8, false, false, true),  ZMPC_LQI(8, true, false, true),
+    ZMPC_LQI(8, true, true, false),   ZMPC_LQI(8, true, true, true),
+    ZMPC_LQI(4, false, false, false), ZMPC_LQI(4, true, false, false),
+    ZMPC_LQI(4, false, false, true),  ZMPC_LQI(4, true, false, true),
+    ZMPC_LQI(2, false, false, false), ZMPC_LQI(2, true, false, false),
+    ZMPC_LQI(2, false, false, true),  ZMPC_LQI(2, true, false, true),
 };
-#undef ZMPC_LQV
-#undef ZMPC_LQP
-#undef ZMPC_LQK
+#undef ZMPC_LQI
 
-// The kernels of a workgroup shape (dispatch.h lq_shape: G = 8, 4 or 2).
-const LqVariant* lq_variant(int G) {
-  for (const LqVariant& c : kLqVariants)
-    if (c.G == G) return &c;
+// The kernel of (G, runs, queue, push), or null where no such instance exists.
+LqKernel lq_kernel(int G, bool runs, bool queue, bool push) {
+  for (const LqInstance& c : kLqInstances)
+    if (c.G == G && c.runs == runs && c.queue == queue && c.push == push) return c.kernel;
   return nullptr;
 }
 
@@ -1315,31 +1282,22 @@ void fill_consts(const zmpc_plan* p, LqArgs& a) {
 
 hipError_t launch_lq(const zmpc_plan* p, LqArgs& a, int64_t waves, hipStream_t s) {
   const LqShape shape = lq_shape(p->N);
-  const LqVariant* var = lq_variant(shape.G);
-  if (!var) return hipErrorInvalidValue;
-  const int64_t blocks = (waves + var->G - 1) / var->G;
+  const int G = shape.G;
+  // (cached checkpoints; bounds by runs or rows; a push window has its own instances; kq: the
+  // same launch's task-queue form, null where there is none)
+  const bool runs = a.rs != nullptr, push = a.push.amp != nullptr;
+  LqKernel k = lq_kernel(G, runs, false, push);
+  const LqKernel kq = lq_kernel(G, runs, true, push);
+  if (!k) return hipErrorInvalidValue;
+  const int64_t blocks = (waves + G - 1) / G;
   a.nlck = shape.nlck;
   size_t lds = shape.lds;
 #ifdef ZMPC_DIAG
   if (const char* e = getenv("ZMPC_LQ_NLCK")) {  // (A/B)
     a.nlck = std::min(a.nlck, atoi(e));
-    lds = lq_lds_bytes(var->G, p->N, a.nlck);
+    lds = lq_lds_bytes(G, p->N, a.nlck);
   }
 #endif
-  // cached checkpoints (see CkIO: with run-length bounds the window rows no longer compete
-  // for the caches, and non-temporal checkpoints became the slower form — config 3 55.4 vs
-  // 56.7 ms, diagnostics build, profiles/r5m/)
-  bool nt = false;
-#ifdef ZMPC_DIAG
-  if (const char* e = getenv("ZMPC_LQ_NT")) nt = atoi(e) != 0;  // (diagnostics: A/B of the policy)
-#endif
-  auto k = a.rs ? (nt ? var->kernel_runs_nt : var->kernel_runs) : (nt ? var->kernel_nt : var->kernel);
-  auto kq = a.rs ? (nt ? var->q_kernel_runs_nt : var->q_kernel_runs)
-                 : (nt ? var->q_kernel_nt : var->q_kernel);
-  if (a.push.amp != nullptr) {  // a push window: its own instances
-    k = a.rs ? var->p_kernel_runs : var->p_kernel;
-    kq = a.rs ? var->p_q_kernel_runs : nullptr;
-  }
   // more blocks than the chip holds at once: a grid of the resident blocks and a task queue
   // (an x wave is done long before its SIMD's y wave; with one task per wave its slot idles
   // until the whole block has finished, while a queue refills it with the next y wave)
@@ -1352,7 +1310,7 @@ hipError_t launch_lq(const zmpc_plan* p, LqArgs& a, int64_t waves, hipStream_t s
 #endif
   if (use_queue && queue != nullptr && kq != nullptr && !a.window_mode) {
     int per_cu = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void*)kq, 64 * var->G, lds) !=
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void*)kq, 64 * G, lds) !=
         hipSuccess) {
       (void)hipGetLastError();
       per_cu = 0;
@@ -1381,7 +1339,7 @@ hipError_t launch_lq(const zmpc_plan* p, LqArgs& a, int64_t waves, hipStream_t s
 #else
   a.prof = nullptr;
 #endif
-  hipLaunchKernelGGL(k, dim3((unsigned)grid), dim3(64 * var->G), lds, s, a,
+  hipLaunchKernelGGL(k, dim3((unsigned)grid), dim3(64 * G), lds, s, a,
                      (const double*)p->lqtab);
   hipError_t e = hipGetLastError();
   if (a.prof && e == hipSuccess) {
@@ -1401,17 +1359,34 @@ hipError_t launch_lq(const zmpc_plan* p, LqArgs& a, int64_t waves, hipStream_t s
   return e;
 }
 
+// One launch's workspace: the checkpoints of every wave of the launched blocks (whole blocks:
+// lq_shape's G) and `rest` doubles behind them, in one stream-ordered allocation that `body(ck,
+// rest)` fills and launches on and that is freed after it on the same stream.  A failed allocation
+// is hipErrorOutOfMemory (ZMPC_ENOMEM at the C-ABI); otherwise the body's error, else the free's.
+template <class Body>
+hipError_t with_lq_workspace(const zmpc_plan* p, const LqArgs& a, int64_t waves, size_t rest,
+                             hipStream_t s, Body body) {
+  const int64_t G = lq_shape(p->N).G;
+  if (G == 0) return hipErrorInvalidValue;
+  const size_t ck_doubles = (size_t)((waves + G - 1) / G * G) * a.NS * kCkStride;
+  double* ws = nullptr;
+  if (hipMallocAsync((void**)&ws, (ck_doubles + rest) * sizeof(double), s) != hipSuccess) {
+    (void)hipGetLastError();
+    return hipErrorOutOfMemory;
+  }
+  const hipError_t e = body(ws, ws + ck_doubles);
+  const hipError_t ef = hipFreeAsync(ws, s);
+  return e != hipSuccess ? e : ef;
+}
+
 }  // namespace
 
 hipError_t zmpc_strict_lq_set_attrs() {
   hipError_t e = hipSuccess;
-  for (const LqVariant& c : kLqVariants)
-    for (auto k : {c.kernel, c.kernel_nt, c.kernel_runs, c.kernel_runs_nt, c.q_kernel,
-                   c.q_kernel_nt, c.q_kernel_runs, c.q_kernel_runs_nt, c.p_kernel, c.p_kernel_runs,
-                   c.p_q_kernel_runs})
-      if (k != nullptr && e == hipSuccess)
-        e = hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                160 * 1024);
+  for (const LqInstance& c : kLqInstances)
+    if (e == hipSuccess)
+      e = hipFuncSetAttribute((const void*)c.kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
+                              160 * 1024);
   return e;
 }
 
@@ -1454,9 +1429,6 @@ hipError_t zmpc_launch_rollout_strict_lq(const zmpc_plan* p, const RolloutCall& 
   const int64_t Bst = a.shared ? 64 : B;  // a shared CoP is staged once, 64 identical lanes
   a.groups = (Bst + 63) / 64;
   a.rows = n + (int64_t)a.NS * LQ_S;  // the last segment reads up to NS·S − 1 ahead
-  const int64_t G = lq_shape(p->N).G;  // checkpoints for every wave of the launched blocks
-  if (G == 0) return hipErrorInvalidValue;
-  const size_t ck_doubles = (size_t)((waves + G - 1) / G * G) * a.NS * kCkStride;
   // bounds: rows (2 axes × rows × 64 (z_ref, half-width)) or runs (per (axis, group) up to
   // n + 2 runs of a pair and a start time).  ZMPC_OPT_STRICT_BOUNDS 0 (auto) = runs
   // (profiles/r4/r4e_*: config 3 71.8 → 64.3 ms with runs, L2 fetch 122 → 24 GB per launch).
@@ -1474,38 +1446,33 @@ hipError_t zmpc_launch_rollout_strict_lq(const zmpc_plan* p, const RolloutCall& 
       p->opt[ZMPC_OPT_KICK_ORDER] != 0 && (c.kick != nullptr || c.push.amp != nullptr) && B > 64;
   const size_t perm_doubles = ordered ? ((size_t)B * 4 + 7) / 8 : 0;
   const size_t ord_doubles = ordered ? (zmpc_kick_order_bytes(B) + 7) / 8 : 0;
-  double* ws = nullptr;
-  if (hipMallocAsync((void**)&ws,
-                     (ck_doubles + st_doubles + perm_doubles + ord_doubles + 1) * sizeof(double),
-                     s) != hipSuccess) {
-    (void)hipGetLastError();
-    return hipErrorOutOfMemory;  // ZMPC_ENOMEM at the C-ABI
-  }
-  a.ck = ws;
-  a.queue = reinterpret_cast<int*>(ws + ck_doubles + st_doubles + perm_doubles + ord_doubles);
-  double2* hl = reinterpret_cast<double2*>(ws + ck_doubles);
-  a.perm = nullptr;
-  if (ordered) {
-    int32_t* perm = reinterpret_cast<int32_t*>(ws + ck_doubles + st_doubles);
-    e = zmpc_kick_order(c.kick, c.kick_steps, c.kick_step, c.push, B, perm,
-                        ws + ck_doubles + st_doubles + perm_doubles, s);
-    a.perm = perm;
-  }
-  if (e == hipSuccess) {
-    const int32_t* perm = a.shared ? nullptr : a.perm;
-    if (runs) {
-      a.rs = hl;
-      a.rt = reinterpret_cast<int*>(hl + 2 * a.groups * a.rstride);
-      e = stage_runs(c.zmax, c.zmin, c.bstride, 2, 1, n, Bst, 2, hl, const_cast<int*>(a.rt),
-                     a.rstride, s, perm);
-    } else {
-      e = stage(c.zmax, c.zmin, c.bstride, 2, 1, n, Bst, a.rows, 2, hl, s, perm);
-      a.hl = hl;
-    }
-  }
-  if (e == hipSuccess) e = launch_lq(p, a, waves, s);
-  hipError_t ef = hipFreeAsync(ws, s);
-  return e != hipSuccess ? e : ef;
+  // behind the checkpoints: staged bounds, permutation, the sort's scratch, the queue's counter
+  return with_lq_workspace(
+      p, a, waves, st_doubles + perm_doubles + ord_doubles + 1, s, [&](double* ck, double* rest) {
+        a.ck = ck;
+        double2* hl = reinterpret_cast<double2*>(rest);
+        int32_t* perm = reinterpret_cast<int32_t*>(rest + st_doubles);
+        double* ord = rest + st_doubles + perm_doubles;
+        a.queue = reinterpret_cast<int*>(ord + ord_doubles);
+        a.perm = nullptr;
+        if (ordered) {
+          e = zmpc_kick_order(c.kick, c.kick_steps, c.kick_step, c.push, B, perm, ord, s);
+          a.perm = perm;
+        }
+        if (e == hipSuccess) {
+          const int32_t* sperm = a.shared ? nullptr : a.perm;
+          if (runs) {
+            a.rs = hl;
+            a.rt = reinterpret_cast<int*>(hl + 2 * a.groups * a.rstride);
+            e = stage_runs(c.zmax, c.zmin, c.bstride, 2, 1, n, Bst, 2, hl, const_cast<int*>(a.rt),
+                           a.rstride, s, sperm);
+          } else {
+            e = stage(c.zmax, c.zmin, c.bstride, 2, 1, n, Bst, a.rows, 2, hl, s, sperm);
+            a.hl = hl;
+          }
+        }
+        return e == hipSuccess ? launch_lq(p, a, waves, s) : e;
+      });
 }
 
 hipError_t zmpc_launch_step_strict_lq(const zmpc_plan* p, const StepCall& c, hipStream_t s,
@@ -1527,21 +1494,12 @@ hipError_t zmpc_launch_step_strict_lq(const zmpc_plan* p, const StepCall& c, hip
   a.groups = (B + 63) / 64;
   a.rows = (int64_t)a.NS * LQ_S;
   const int64_t waves = (B + 63) / 64;
-  const int64_t G = lq_shape(p->N).G;  // checkpoints for every wave of the launched blocks
-  if (G == 0) return hipErrorInvalidValue;
-  const size_t ck_doubles = (size_t)((waves + G - 1) / G * G) * a.NS * kCkStride;
-  const size_t st_doubles = (size_t)a.groups * a.rows * 64 * 2;  // (hi, lo)
-  double* ws = nullptr;
-  if (hipMallocAsync((void**)&ws, (ck_doubles + st_doubles) * sizeof(double), s) != hipSuccess) {
-    (void)hipGetLastError();
-    return hipErrorOutOfMemory;  // ZMPC_ENOMEM at the C-ABI
-  }
-  hipError_t e = hipSuccess;
-  a.ck = ws;
-  double2* hl = reinterpret_cast<double2*>(ws + ck_doubles);
-  e = stage(c.zmax_win, c.zmin_win, p->N, 1, 0, p->N, B, a.rows, 1, hl, s);
-  a.hl = hl;
-  if (e == hipSuccess) e = launch_lq(p, a, waves, s);
-  hipError_t ef = hipFreeAsync(ws, s);
-  return e != hipSuccess ? e : ef;
+  const size_t st_doubles = (size_t)a.groups * a.rows * 64 * 2;  // (z_ref, half-width)
+  return with_lq_workspace(p, a, waves, st_doubles, s, [&](double* ck, double* rest) {
+    a.ck = ck;
+    double2* hl = reinterpret_cast<double2*>(rest);
+    a.hl = hl;
+    const hipError_t e = stage(c.zmax_win, c.zmin_win, p->N, 1, 0, p->N, B, a.rows, 1, hl, s);
+    return e == hipSuccess ? launch_lq(p, a, waves, s) : e;
+  });
 }

@@ -35,6 +35,7 @@
 #include <algorithm>
 #include <cstdio>
 #include <cstdlib>
+#include <utility>
 
 #include "strict_eta.h"
 #include "zmpc_internal.h"
@@ -43,7 +44,6 @@ namespace {
 
 using namespace zmpc_eta;
 
-constexpr int SC_MAXIT = 1024;  // active-set pass cap (as strict_lq.hip)
 // (the horizons of the kernel, kScan32MaxN and kScanMaxN, are in dispatch.h)
 
 struct ScanArgs {
@@ -611,7 +611,7 @@ __global__ void __launch_bounds__(64, (C >= ZMPC_SCAN_ONE_WAVE_C ? 1 : 2))
         ++it;
         if (!ich) {
           mine = false;
-        } else if (it >= SC_MAXIT) {
+        } else if (it >= kStrictMaxPasses) {
           fq |= ZMPC_ST_MAXITER;
           mine = false;
         }
@@ -694,10 +694,22 @@ void fill(const zmpc_plan* p, ScanArgs& a) {
   a.cnt = p->lqcnt;
 }
 
-// The kernel instance of dispatch.h scan_shape (lanes per instance, slots per lane).  Chunks of
-// C ≥ 3 slots per lane hold 1 wave per SIMD (their state spills past 256 VGPRs into AGPRs instead
-// of scratch: __launch_bounds__ above), shorter ones 2.  (C = 3 at 2 waves per SIMD spilled 12 B
-// to scratch; 1024 walks at N = 150, 32 lanes at one wave per SIMD: 10.2 → 6.2 ms, profiles/r5q/.)
+// Calls fn(std::integral_constant<int, C>) for the slots per lane C = c in 1..CMAX; false: no such
+// instance (as rollout.hip's with_cw).
+template <int... I, class F>
+bool with_c(std::integer_sequence<int, I...>, int c, F&& fn) {
+  return ((c == I + 1 && (fn(std::integral_constant<int, I + 1>{}), true)) || ...);
+}
+template <int CMAX, class F>
+bool with_c(int c, F&& fn) {
+  return with_c(std::make_integer_sequence<int, CMAX>{}, c, fn);
+}
+
+// The kernel instance of dispatch.h scan_shape (lanes per instance, slots per lane: C ≤ 16 at 32
+// lanes, C ≤ 15 at 64).  Chunks of C ≥ 3 slots per lane hold 1 wave per SIMD (their state spills
+// past 256 VGPRs into AGPRs instead of scratch: __launch_bounds__ above), shorter ones 2.  (C = 3 at
+// 2 waves per SIMD spilled 12 B to scratch; 1024 walks at N = 150, 32 lanes at one wave per SIMD:
+// 10.2 → 6.2 ms, profiles/r5q/.)
 hipError_t launch(const zmpc_plan* p, const ScanArgs& a, hipStream_t s) {
   const ScanShape shape = scan_shape(p->N, a.ninst, p->cus);
   const dim3 blk(64);
@@ -705,36 +717,19 @@ hipError_t launch(const zmpc_plan* p, const ScanArgs& a, hipStream_t s) {
 #ifdef ZMPC_DIAG
   if (const char* e = getenv("ZMPC_SCAN_CMIN")) cmin = atoi(e);  // (diagnostics: wider chunks)
 #endif
+  bool found;
   if (shape.lanes == 32) {
     const dim3 grid((unsigned)((a.ninst + 1) / 2));
-    switch (std::max(shape.C, std::min(cmin, 16))) {
-#define ZMPC_SCASE(CC)                                                        \
-  case CC:                                                                    \
-    hipLaunchKernelGGL((zmpc_strict_scan_kernel<CC, 32>), grid, blk, 0, s, a); \
-    break;
-      ZMPC_SCASE(1) ZMPC_SCASE(2) ZMPC_SCASE(3) ZMPC_SCASE(4) ZMPC_SCASE(5) ZMPC_SCASE(6)
-      ZMPC_SCASE(7) ZMPC_SCASE(8) ZMPC_SCASE(9) ZMPC_SCASE(10) ZMPC_SCASE(11) ZMPC_SCASE(12)
-      ZMPC_SCASE(13) ZMPC_SCASE(14) ZMPC_SCASE(15) ZMPC_SCASE(16)
-#undef ZMPC_SCASE
-      default:
-        return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
+    found = with_c<16>(std::max(shape.C, std::min(cmin, 16)), [&](auto C) {
+      hipLaunchKernelGGL((zmpc_strict_scan_kernel<decltype(C)::value, 32>), grid, blk, 0, s, a);
+    });
+  } else {
+    const dim3 grid((unsigned)a.ninst);
+    found = with_c<15>(shape.C, [&](auto C) {
+      hipLaunchKernelGGL((zmpc_strict_scan_kernel<decltype(C)::value, 64>), grid, blk, 0, s, a);
+    });
   }
-  const dim3 grid((unsigned)a.ninst);
-  switch (shape.C) {
-#define ZMPC_SCASE(CC)                                                        \
-  case CC:                                                                    \
-    hipLaunchKernelGGL((zmpc_strict_scan_kernel<CC, 64>), grid, blk, 0, s, a); \
-    break;
-    ZMPC_SCASE(1) ZMPC_SCASE(2) ZMPC_SCASE(3) ZMPC_SCASE(4) ZMPC_SCASE(5) ZMPC_SCASE(6)
-    ZMPC_SCASE(7) ZMPC_SCASE(8) ZMPC_SCASE(9) ZMPC_SCASE(10) ZMPC_SCASE(11) ZMPC_SCASE(12)
-    ZMPC_SCASE(13) ZMPC_SCASE(14) ZMPC_SCASE(15)
-#undef ZMPC_SCASE
-    default:
-      return hipErrorInvalidValue;
-  }
-  return hipGetLastError();
+  return found ? hipGetLastError() : hipErrorInvalidValue;
 }
 
 }  // namespace

@@ -36,9 +36,9 @@ static const double* g_tab;
 static bool g_runs = true;
 static void lane_main() {
   if (g_runs)
-    emu::zmpc_strict_lq_kernel<8, 1, false, true, false>(g_args, g_tab);
+    emu::zmpc_strict_lq_kernel<8, 1, true, false>(g_args, g_tab);
   else
-    emu::zmpc_strict_lq_kernel<8, 1, false, false, false>(g_args, g_tab);
+    emu::zmpc_strict_lq_kernel<8, 1, false, false>(g_args, g_tab);
   g_done[g_cur] = true;
 }
 

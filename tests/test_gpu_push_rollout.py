@@ -11,6 +11,7 @@ status asserted; Herdt CoM RMSE and feet 1e-9, histories 1e-8; unconstrained CoM
 1e-7; forms that compute the same solution agree to 1e-11 (include/zmpc.h)."""
 import ctypes
 import functools
+import os
 
 import numpy as np
 import pytest
@@ -294,6 +295,30 @@ def test_long_horizon_lq_shape():
     ref = np.stack([pr.strict_walk(case, b, sc.WEIGHTS[0], pr.window(6, 0, 3, w, amp))
                     for b in range(3)])
     assert_hist(h, st, ref, "lq_rollout_case(321) D=3")
+
+
+@pytest.mark.parametrize("N", (897, 2177))
+def test_lq_push_instances_of_short_workgroups(N):
+    """The LQ kernel's push instances of 4 and 2 waves per workgroup (N = 897, 2177; csrc/dispatch.h
+    lq_shape), in both bound forms: lq_rollout_case(N) with its kick given as a D = 1 push on y
+    with the profile [1.0] (a profile, so not the legacy kick: the push instance runs).  That is
+    the kick itself (include/zmpc.h, "The push, stated once"; amp·1.0 is exact), so the reference
+    is the C restatement of the kicked rollout, as test_gpu_strict_cases.py test_lq_shapes."""
+    case = sc.lq_rollout_case(N)
+    ref, cst, _ = sc.restatement(case, threads=min(16, os.cpu_count() or 1))
+    assert not cst.any()
+    p = strict_plan(N, case["dt"], solver=3)
+    outs = []
+    try:
+        for bounds in (1, 2):
+            p.set_option("strict_bounds", bounds)
+            h, st = pushed(p, case["zmax"], case["zmin"], case["x0"], case["kick"][:, None], "y",
+                           steps=case["kick_step"], w=np.ones(1), D=1)
+            assert_hist(h, st, ref, f"lq push instance N={N} bounds {bounds}")
+            outs.append(h)
+    finally:
+        p.set_option("strict_bounds", 0)
+    print(f"MEASURED lq push instance N={N}: bound forms bitwise equal {same_bits(*outs)}")
 
 
 def test_asymmetric_profile_strict():

@@ -138,7 +138,7 @@ _DIAG_ENV = ("ZMPC_DEBUG_LQ", "ZMPC_DEBUG_ROLLOUT", "ZMPC_DEBUG_PLAN", "ZMPC_DEB
              "ZMPC_STRICT_LQ_DRIFT", "ZMPC_STRICT_ORDER", "ZMPC_STRICT_VARIANT", "ZMPC_SPARSE_CORR",
              "ZMPC_FFT", "ZMPC_NO_FFT", "ZMPC_ROLLOUT_NO_WIDE", "ZMPC_NO_SHARED_F",
              "ZMPC_PREFETCH", "ZMPC_PF_ROUNDS", "ZMPC_PERS_PER_CU", "ZMPC_HERDT_WARM",
-             "ZMPC_HERDT_PROF", "ZMPC_STRICT_LDS_G", "ZMPC_STRICT_LDS_CHOL")
+             "ZMPC_HERDT_PROF", "ZMPC_STRICT_LDS_G", "ZMPC_STRICT_LDS_CHOL", "ZMPC_LQ_NT")
 
 
 def test_product_library_reads_no_result_changing_environment():
