@@ -572,6 +572,55 @@ int zmpc_herdt_walk_metrics(const zmpc_plan* plan, const zmpc_herdt_params* para
                             double* metrics, void* stream);
 
 /*
+ * Footstep bookkeeping of a batch of Herdt walks with different gaits, on the device: the two
+ * inputs of zmpc_herdt_rollout(_pushed) that follow from the support states alone — nb_next
+ * (zmp_controller.py:203-433, :466-470) and the footstep count that sizes the kernel instance
+ * (zmpc_herdt_params.max_footsteps; the phase breaks of :561-573) — which the host otherwise
+ * makes one walk at a time.
+ *
+ * This call takes no stream and is synchronous, like zmpc_plan_counters, zmpc_plan_export and
+ * zmpc_plan_destroy: *max_footsteps_host has to reach the host before the rollout it prepares can
+ * be sized.  It synchronises the plan's device on entry, so whatever stream produced `states`
+ * has finished, and it returns when every output is complete.  The plan supplies N and the device;
+ * any plan kind serves.
+ *
+ * The walk, stated once, in terms of walk b's own sequence, not the batch's:
+ *   - n_b = clamp(lengths[b], 1, n), or n with NULL lengths.
+ *   - c[i] = states[b, min(i, n_b − 1)] for 0 <= i < L, L = n_b + N: the live walk followed by N
+ *     copies of its last live state, what the reference builds for that walk alone (:466-469).
+ *     Rows at or past n_b of the input are never read (zmpc_cop_generate's −1 padding lives there),
+ *     so a walk padded to the batch's n gives what the walk alone gives.
+ *   states     : [B, n] int8 device (s_stride bytes between walks; 0 = one schedule shared by
+ *                every walk, only `lengths` can then make the rows differ)
+ *   lengths    : [B] int64 device, or NULL
+ *   states_out : [B, n] int8 device, or NULL: states_out[b, i] = c[i] for i < n — the states a
+ *                rollout of the padded batch reads in walk b's place.  Must not overlap `states`.
+ *   nb_next    : [B, n] int32 device.  For i < n_b the first element of find_nb_steps on c[0..L):
+ *                with nds the smallest j > i, j < L, with c[j] == DOUBLE_SUPPORT and nss(j) the
+ *                same for SINGLE_SUPPORT,
+ *                  c[i] == STANDING: L − i with no nds; else with q = nss(nds), L − i with no q,
+ *                                    else q − i − 1
+ *                  any other code:   nds − i if nds exists, else L − i
+ *                (the "next" index may lie in the tail: a walk may end in double or single
+ *                support).  nb_next[b, i] = 1 for n_b <= i < n: those rows' windows are constant,
+ *                hold no footstep, and the rollout never divides by the value.
+ *   max_steps  : [B] int32 device, or NULL: the maximum over 0 <= i < max(n_b − 1, 1) of the
+ *                number of t in [i, i + N) with c[t] != c[t+1] and not (c[t] DOUBLE_SUPPORT and
+ *                c[t+1] SINGLE_SUPPORT) — the most footsteps in one horizon window of that walk
+ *   max_footsteps_host : one int32 in HOST memory, or NULL: the maximum of max_steps over the
+ *                batch, 0 for B = 0.  A value above 8 is reported, not refused: the rollout's
+ *                parameter check refuses it.
+ * Results are integers; two calls on the same input agree.  Workspace: one device word.
+ * ZMPC_EINVAL, decided from the arguments before any device call and before the plan is read:
+ * NULL plan; B < 0; n < 1; n beyond zmpc_rollout's limit ("walk too long"); (B > 0) NULL states
+ * or nb_next; a non-zero s_stride < n.  B = 0 writes the host word and nothing else.  Additive to
+ * ABI 7.
+ */
+int zmpc_herdt_prepare(const zmpc_plan* plan, int64_t B, int64_t n, const int8_t* states,
+                       int64_t s_stride, const int64_t* lengths, int8_t* states_out,
+                       int32_t* nb_next, int32_t* max_steps, int32_t* max_footsteps_host);
+
+/*
  * Batched predict_herdt_joint (zmp_controller.py:533-826), one QP per instance, cold start:
  *   x [B, 2, 3] (x, y) states; v_win [B, N, 2] window of v_ref; s_win [B, N] window states;
  *   current [B] int8 current support state; foot [B, 2] current foot (x_fc, y_fc);

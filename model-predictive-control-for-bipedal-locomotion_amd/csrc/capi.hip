@@ -670,6 +670,42 @@ int zmpc_herdt_walk_metrics(const zmpc_plan* P, const zmpc_herdt_params* prm, in
   return ZMPC_OK;
 }
 
+int zmpc_herdt_prepare(const zmpc_plan* P, int64_t B, int64_t n, const int8_t* states,
+                       int64_t s_stride, const int64_t* lengths, int8_t* states_out,
+                       int32_t* nb_next, int32_t* max_steps, int32_t* max_footsteps_host) {
+  g_err.clear();
+  if (!P) return fail(ZMPC_EINVAL, "NULL plan");
+  if (B < 0 || n < 1) return fail(ZMPC_EINVAL, "need B >= 0 and n >= 1");
+  if (n > (1 << 24)) return fail(ZMPC_EINVAL, "walk too long");
+  if (B > 0x7fffffff) return fail(ZMPC_EINVAL, "batch too large");
+  if (B > 0 && (!states || !nb_next)) return fail(ZMPC_EINVAL, "NULL array argument");
+  if (s_stride != 0 && s_stride < n)
+    return fail(ZMPC_EINVAL, "s_stride must be 0 (shared) or >= n");
+  if (max_footsteps_host) *max_footsteps_host = 0;
+  if (B == 0) return ZMPC_OK;
+  DeviceGuard g(P->device);
+  if (g.err != hipSuccess) return hip_fail(g.err, "hipSetDevice");
+  // whatever stream produced `states` has finished before the kernel reads them
+  hipError_t e = hipDeviceSynchronize();
+  if (e != hipSuccess) return hip_fail(e, "hipDeviceSynchronize");
+  int32_t* word = nullptr;  // the batch's largest footstep count
+  if (max_footsteps_host) {
+    if (hipMalloc(&word, sizeof(int32_t)) != hipSuccess)
+      return fail(ZMPC_ENOMEM, "zmpc_herdt_prepare: device workspace allocation failed");
+    e = hipMemset(word, 0, sizeof(int32_t));
+  }
+  if (e == hipSuccess)
+    e = zmpc_launch_herdt_prepare(P, B, n, states, s_stride, lengths, states_out, nb_next,
+                                  max_steps, word, nullptr);
+  // every output is complete when the call returns (the copy of the word waits for the kernel)
+  if (e == hipSuccess)
+    e = word ? hipMemcpy(max_footsteps_host, word, sizeof(int32_t), hipMemcpyDeviceToHost)
+             : hipDeviceSynchronize();
+  if (word) (void)hipFree(word);
+  if (e != hipSuccess) return hip_fail(e, "zmpc_herdt_prepare");
+  return ZMPC_OK;
+}
+
 int zmpc_herdt_step(const zmpc_plan* P, const zmpc_herdt_params* prm, int64_t B,
                     const double* x, const double* v_win, const int8_t* s_win,
                     const int8_t* current, const double* foot, const int8_t* side,

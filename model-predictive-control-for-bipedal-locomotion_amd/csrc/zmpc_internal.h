@@ -172,6 +172,15 @@ hipError_t zmpc_launch_herdt_walk_metrics(const zmpc_plan* p, const zmpc_herdt_p
                                           int64_t rstride, const int64_t* lengths, double tol,
                                           double* metrics, hipStream_t s);
 
+// footstep bookkeeping of a batch of Herdt walks (herdt_prep.hip): one wavefront per walk, reads
+// only p->N; lengths, states_out and max_steps may be NULL; batch_max: one device word that
+// holds 0 and receives the largest max_steps of the batch, or NULL
+hipError_t zmpc_launch_herdt_prepare(const zmpc_plan* p, int64_t B, int64_t n,
+                                     const int8_t* states, int64_t sstride,
+                                     const int64_t* lengths, int8_t* states_out,
+                                     int32_t* nb_next, int32_t* max_steps, int32_t* batch_max,
+                                     hipStream_t s);
+
 // The arguments of one zmpc_push_map / zmpc_push_map_shaped call (zmpc_push_map: duration 1, no
 // profile, the y axis).
 struct PushCall {

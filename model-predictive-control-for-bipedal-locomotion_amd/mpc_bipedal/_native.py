@@ -116,6 +116,9 @@ SIGNATURES = {
     # ... x0, push (const zmpc_push*), hist, foot, status, stream
     "zmpc_herdt_rollout_pushed": (_C, [_P, _P, _L, _L, _P, _L, _P, _L, _P, _L, _P, _P, _P, _P,
                                        _P, _P]),
+    # plan, B, n, states, s_stride, lengths, states_out, nb_next, max_steps, max_footsteps (host);
+    # no stream: synchronous, called as zmpc_plan_export is
+    "zmpc_herdt_prepare": (_C, [_P, _L, _L, _P, _L, _P, _P, _P, _P, ctypes.POINTER(_I)]),
     "zmpc_herdt_step": (_C, [_P, _P, _L, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     # params, B, n, hist, foot, states, s_stride, foot_ref, foot_ref_stride, lengths, count_tol,
     # metrics, stream

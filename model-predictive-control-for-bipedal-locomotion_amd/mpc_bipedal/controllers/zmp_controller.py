@@ -219,38 +219,87 @@ class ZMPController:
         return xn[0].reshape(3, 1), xn[1].reshape(3, 1), fx, fy
 
     def generate_com_trajectory_herdt_batch(self, x_init, v_ref, state_ref, F_ext=None,
-                                            return_status: bool = False, push: Push = None):
+                                            return_status: bool = False, push: Push = None,
+                                            walk_lengths=None):
         """Many Herdt walks at once (addition): x_init [B,2,3] or None; v_ref [B,n,2] or a
-        shared [n,2]; state_ref [B,n] or a shared [n] (State enums or int8 codes); F_ext [B]
-        or None.  Returns (com [B,n,2], hist [B,n,2,3], foot [B,n,2]) on the device; with
-        return_status=True also the per-walk status [B] (ZMPC_ST_* flags) instead of raising
-        or warning on a failed walk.  push: an analysis.Push — a shove of any length, shape and
-        direction instead of F_ext (zmpc_herdt_rollout_pushed; not together with F_ext)."""
+        shared [n,2]; state_ref [B,n] or a shared [n] (State enums or int8 codes, NumPy or a
+        device tensor, which stays on the device); F_ext [B] or None.  Returns (com [B,n,2],
+        hist [B,n,2,3], foot [B,n,2]) on the device; with return_status=True also the per-walk
+        status [B] (ZMPC_ST_* flags) instead of raising or warning on a failed walk.  push: an
+        analysis.Push — a shove of any length, shape and direction instead of F_ext
+        (zmpc_herdt_rollout_pushed; not together with F_ext).  The footstep bookkeeping of the
+        walks (nb_next, the footstep count that sizes the kernel) is made on the device
+        (zmpc_herdt_prepare), whatever their gaits.
+
+        walk_lengths : [B] sample counts of ragged walks padded to n
+                (SpeedTrajectoryGenerator.generate_speed_and_state_batch): walk b is then rows
+                [0, n_b) alone — its states and v_ref rows at or past n_b are replaced by row
+                n_b − 1, which is what the walk alone sees through the rollout's last-row
+                padding, and F_ext hits step n_b // 2 of each walk.  Output rows at or past n_b
+                are unspecified but finite."""
         if push is not None and F_ext is not None:
             raise ValueError("give either F_ext or push, not both")
         v = torch.as_tensor(v_ref, dtype=torch.float64)
         n = int(v.shape[-2])
-        st = herdt.encode_states(state_ref) if not isinstance(state_ref, torch.Tensor) \
-            else state_ref.cpu().numpy().astype(np.int8)
+        st = self._herdt_codes(state_ref)
         if x_init is not None:
             B = int(np.shape(x_init)[0])
         elif v.dim() == 3:
             B = int(v.shape[0])
         elif st.ndim == 2:
             B = int(st.shape[0])
+        elif walk_lengths is not None:
+            B = int(np.shape(walk_lengths)[0])
         elif push is not None:
             B = push.batch() or 1
         else:
             B = 1 if F_ext is None else int(np.size(F_ext))
         x0 = np.zeros((B, 2, 3)) if x_init is None else x_init
         kick = None
-        if F_ext is not None:
+        if F_ext is not None and walk_lengths is None:
             kick = self.config.dt * np.asarray(F_ext, np.float64).reshape(B) / self.config.m
+        elif F_ext is not None:
+            # a kick step per walk: the legacy push of the pushed entry point, at n_b // 2
+            steps = _default_force_step(n, self._lengths_host(walk_lengths, B, n))
+            push = Push(np.asarray(F_ext, np.float64).reshape(B), +1, steps)
         hist, foot, status = self._herdt_rollout(x0, v_ref, st, kick, n // 2,
-                                                 check=not return_status, push=push)
+                                                 check=not return_status, push=push,
+                                                 on_device=True, lengths=walk_lengths)
         if return_status:
             return hist[..., 0], hist, foot, status
         return hist[..., 0], hist, foot
+
+    @staticmethod
+    def _herdt_codes(state_ref):
+        """State enums, their names or int8 codes → int8 NumPy codes; a tensor stays where it
+        is."""
+        return state_ref if isinstance(state_ref, torch.Tensor) else herdt.encode_states(state_ref)
+
+    @staticmethod
+    def _lengths_host(walk_lengths, B, n):
+        """walk_lengths as [B] int64 on the host, clamped to [1, n] as the kernels clamp them."""
+        t = walk_lengths.cpu().numpy() if isinstance(walk_lengths, torch.Tensor) else walk_lengths
+        return np.clip(np.asarray(t, np.int64).reshape(B), 1, n)
+
+    def _herdt_device(self, plan, st, v_ref, lengths=None):
+        """The preparation of a batched Herdt rollout on the device (Plan.herdt_prepare): (params
+        sized by the most footsteps in a window of any walk, states, nb_next, v_ref).  With
+        lengths [B] the states are walk b's own, continued by its last live state, and so are
+        the rows of v_ref (a gather on the device)."""
+        clean, nb, _, most = plan.herdt_prepare(st, lengths)
+        prm = herdt.make_params(self.config, most)
+        if lengths is None:
+            return prm, clean, nb, v_ref
+        dev = clean.device
+        v = torch.as_tensor(v_ref, dtype=torch.float64, device=dev)
+        B, n = clean.shape
+        last = torch.as_tensor(lengths, dtype=torch.int64, device=dev).reshape(B).clamp(1, n) - 1
+        rows = torch.minimum(torch.arange(n, device=dev)[None, :], last[:, None])
+        if v.dim() == 2 and v.shape[0] == n:
+            v = v[rows]
+        elif v.dim() == 3 and tuple(v.shape) == (B, n, 2):
+            v = torch.gather(v, 1, rows[:, :, None].expand(B, n, 2))
+        return prm, clean, nb, v  # (any other shape: Plan.herdt_rollout names it)
 
     def _herdt_host(self, plan, st):
         """The host preparation of a Herdt rollout from the int8 states [B, n] or [n]: (params
@@ -263,9 +312,13 @@ class ZMPController:
         nb = np.array([[t[0] for t in herdt.find_nb_steps(p)][:n] for p in pad], np.int32)
         return prm, (nb[0] if st.ndim == 1 else nb)
 
-    def _herdt_rollout(self, x0, v_ref, st, kick, kick_step, check=True, push=None):
+    def _herdt_rollout(self, x0, v_ref, st, kick, kick_step, check=True, push=None,
+                       on_device=False, lengths=None):
         plan = self._plan()
-        prm, nb = self._herdt_host(plan, st)
+        if on_device:
+            prm, st, nb, v_ref = self._herdt_device(plan, st, v_ref, lengths)
+        else:
+            prm, nb = self._herdt_host(plan, st)
         hist, foot, status = plan.herdt_rollout(prm, v_ref, st, nb, x0, kick=kick,
                                                 kick_step=kick_step, push=push,
                                                 mass=self.config.m)
@@ -517,13 +570,6 @@ class ZMPController:
         return torch.where(never, nan, lo), torch.where(never, nan, hi)
 
     # ------------------------------------------------------------------ Herdt robustness
-    @staticmethod
-    def _herdt_states(state_ref):
-        """State enums, their names, int8 codes or a tensor of codes → int8 NumPy codes."""
-        if isinstance(state_ref, torch.Tensor):
-            return state_ref.cpu().numpy().astype(np.int8)
-        return herdt.encode_states(state_ref)
-
     def herdt_walk_metrics(self, hist, foot, state_ref, foot_ref=None,
                            walk_lengths=None) -> HerdtWalkMetrics:
         """Did a Herdt walk stay up (addition; zmpc_herdt_walk_metrics)?  The support box of a
@@ -542,12 +588,12 @@ class ZMPController:
         f = torch.as_tensor(foot, dtype=torch.float64, device=dev).contiguous()
         prm = herdt.make_params(self.config, 0)
         return HerdtWalkMetrics(plan.herdt_walk_metrics(
-            prm, h, f, self._herdt_states(state_ref), lengths=walk_lengths, foot_ref=foot_ref))
+            prm, h, f, self._herdt_codes(state_ref), lengths=walk_lengths, foot_ref=foot_ref))
 
     def critical_force_herdt(self, v_ref, state_ref, max_dcm_dev, x_init=None, force_step=None,
                              direction=+1, F_hi: float = 1000.0, iters: int = 30,
                              max_violation: float = 1e-9, max_com_dev: Optional[float] = None,
-                             duration: int = 1, profile=None):
+                             duration: int = 1, profile=None, walk_lengths=None):
         """Largest shove each scenario of the footstep-adapting controller survives (addition):
         critical_force for Herdt walks, with its bisection, bracket and NaN conventions.
 
@@ -566,7 +612,13 @@ class ZMPController:
         exponentially on one that does not, so any bound of a step length or so (1 m, say) gives
         nearly the same force.
 
-        The host preparation (padded states, nb_next, max_footsteps) is done once.  Each of the
+        walk_lengths: [B] sample counts of ragged walks padded to n, as
+        generate_com_trajectory_herdt_batch takes them: scenario b is walk b alone (its states and
+        v_ref rows continued by row n_b − 1), the default force_step is n_b // 2 of each walk and
+        the metrics cover its own n_b samples.
+
+        The preparation (padded states, nb_next, max_footsteps) is done once, on the device
+        (zmpc_herdt_prepare), whatever the walks' gaits.  Each of the
         iters + 2 evaluations is one zmpc_herdt_rollout_pushed into reused buffers, its [B, C]
         amplitudes scaled on the device, and one zmpc_herdt_walk_metrics launch; nothing is
         copied to the host inside the loop.  The unpushed evaluation comes first and its feet are
@@ -590,8 +642,8 @@ class ZMPController:
         f64 = dict(dtype=torch.float64, device=dev)
         v = torch.as_tensor(v_ref, **f64).contiguous()
         n = int(v.shape[-2])
-        st = self._herdt_states(state_ref)
-        sized = (force_step, _direction_size(direction, unit))
+        st = self._herdt_codes(state_ref)
+        sized = (force_step, _direction_size(direction, unit), walk_lengths)
         sizes = [int(np.shape(a)[0]) for a in sized if a is not None and np.ndim(a) == 1]
         if x_init is not None:
             B = int(np.shape(x_init)[0])
@@ -606,7 +658,8 @@ class ZMPController:
                              "directions [1, 2] or [B, 2])")
         x0 = torch.zeros((B, 2, 3), **f64) if x_init is None else torch.as_tensor(x_init, **f64)
         if force_step is None:
-            step = n // 2
+            step = _default_force_step(n, None if walk_lengths is None else
+                                       self._lengths_host(walk_lengths, B, n))
         elif np.ndim(force_step) == 0:
             step = int(force_step)
         else:
@@ -618,7 +671,7 @@ class ZMPController:
             sign = np.sign(np.broadcast_to(np.asarray(direction, np.float64), (B,)))
             d1 = np.stack([np.zeros(B), np.where(sign == 0, 1.0, sign)], axis=1)
             F1 = np.abs(sign)  # (sign 0: no push, through a zero force)
-        prm, nb = self._herdt_host(plan, st)
+        prm, st, nb, v = self._herdt_device(plan, st, v, walk_lengths)
         launch = plan.herdt_rollout_launcher(prm, v, st, nb, x0,
                                              Push(F1, d1, step, duration=D, profile=w),
                                              self.config.m)
@@ -626,7 +679,7 @@ class ZMPController:
         metrics = torch.empty((B, NHERDT_METRICS), **f64)
         foot_ref = torch.empty_like(launch.foot)
         measure0, measure = (plan.herdt_walk_metrics_launcher(
-            prm, launch.hist, launch.foot, launch.states, foot_ref=ref,
+            prm, launch.hist, launch.foot, launch.states, lengths=walk_lengths, foot_ref=ref,
             count_tol=max_violation, out=metrics) for ref in (None, foot_ref))
         m = HerdtWalkMetrics(metrics)
 

@@ -11,7 +11,7 @@ from typing import List, Tuple
 
 import numpy as np
 
-from .cop_generator import CoPGenerator, State
+from .cop_generator import CoPGenerator, State, cop_params, generate_cop_batch
 from ..config import MPCConfig
 
 
@@ -51,3 +51,32 @@ class SpeedTrajectoryGenerator:
         if self.config.strict:
             self._zmp_controller._raise_on_status(st)
         return hist[:, :, 0, 1], hist[:, :, 1, 1]
+
+    def generate_speed_and_state_batch(self, params, device: int = 0):
+        """generate_speed_and_state for many different walks at once, on the device: the CoP
+        producer (generate_cop_batch; params as there: MPCConfig-like objects or a [B, 7] array)
+        followed by the speeds of ``config.speed_generation``.  Returns (v_ref [B, n, 2], states
+        [B, n] int8, lengths [B] int64) device tensors: walk b is rows [0, n_b), the states past
+        it are −1 — what ZMPController.generate_com_trajectory_herdt_batch takes with
+        walk_lengths.  The controller's plan is built for ``config.dt``: the dt column of params
+        must equal it (ValueError otherwise)."""
+        import torch
+        mode = (self.config.speed_generation or "wieber").lower()
+        if mode not in ("classic", "wieber"):
+            raise ValueError(f"Unknown speed_generation mode: {self.config.speed_generation}")
+        if not isinstance(params, np.ndarray) and not hasattr(params, "shape"):
+            params = [cop_params(c) for c in params]
+        p = np.asarray(params.cpu() if isinstance(params, torch.Tensor) else params, np.float64)
+        if p.ndim != 2 or p.shape[1] != 7:
+            raise ValueError(f"params must be [B, 7], got {tuple(p.shape)}")
+        if np.any(p[:, 6] != float(self.config.dt)):
+            raise ValueError(f"the dt column of params must equal config.dt = {self.config.dt}: "
+                             "the speeds come from this configuration's controller")
+        z_max, z_min, lengths, states = generate_cop_batch(p, device)
+        if mode == "wieber":
+            v_x, v_y = self.generate_speed_batch(z_max, z_min)
+            return torch.stack([v_x, v_y], dim=-1), states, lengths
+        v = torch.zeros(tuple(states.shape) + (2,), dtype=torch.float64, device=states.device)
+        v[..., 0] = 0.3
+        v[..., 0].masked_fill_(states == 0, 0.0)  # (0: STANDING)
+        return v, states, lengths

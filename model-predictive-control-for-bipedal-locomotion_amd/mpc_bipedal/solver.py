@@ -513,6 +513,41 @@ class Plan:
             raise ValueError(f"states must be [B, n] = [{B}, {n}] or [n], got {tuple(st.shape)}")
         return st, (0 if st.dim() == 1 else n)
 
+    def herdt_prepare(self, states, lengths=None):
+        """Footstep bookkeeping of a batch of Herdt walks on the device (zmpc_herdt_prepare,
+        include/zmpc.h) → (states int8 [B, n], nb_next int32 [B, n], max_steps int32 [B],
+        max_footsteps int): what herdt_rollout takes as states and nb_next, the most footsteps in
+        one horizon window of each walk, and of the batch (HerdtParams.max_footsteps).
+
+        states: [B, n] support codes of B different walks, or a shared [n] (NumPy or a tensor; a
+        tensor on the plan's device is never copied to the host); lengths: [B] live samples of
+        ragged walks or None — walk b is then its own n_b samples padded with its last live state,
+        whatever rows n_b.. of the input hold.  A shared [n] input without lengths gives [n], [n]
+        and [1]; with lengths [B] it is one schedule cut at B lengths.  Synchronous: the call
+        waits for the device on entry and returns with every output complete."""
+        st = torch.as_tensor(np.asarray(states, dtype=np.int8) if not isinstance(
+            states, torch.Tensor) else states, dtype=torch.int8, device=self._device).contiguous()
+        if st.dim() not in (1, 2) or st.shape[-1] < 1:
+            raise ValueError(f"states must be [B, n] or [n] with n >= 1, got {tuple(st.shape)}")
+        n = int(st.shape[-1])
+        shared = st.dim() == 1
+        if shared:
+            B = 1 if lengths is None else int(np.shape(lengths)[0])
+        else:
+            B = int(st.shape[0])
+        len_t = self._index(lengths, B, "lengths")
+        clean = torch.empty((B, n), dtype=torch.int8, device=self._device)
+        nb = torch.empty((B, n), dtype=torch.int32, device=self._device)
+        steps = torch.empty(B, dtype=torch.int32, device=self._device)
+        most = ctypes.c_int32(0)
+        rc = _native.load().zmpc_herdt_prepare(self._live(), B, n, _ptr(st), 0 if shared else n,
+                                               _ptr(len_t), _ptr(clean), _ptr(nb), _ptr(steps),
+                                               ctypes.byref(most))
+        _native.check(rc, "zmpc_herdt_prepare")
+        if shared and lengths is None:
+            clean, nb = clean[0], nb[0]
+        return clean, nb, steps, int(most.value)
+
     def _herdt_walk_metrics_args(self, params, hist, foot, states, lengths, foot_ref, count_tol,
                                  out):
         """The checked arguments of zmpc_herdt_walk_metrics → (out, its arguments without the
