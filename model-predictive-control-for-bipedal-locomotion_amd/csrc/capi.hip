@@ -575,7 +575,8 @@ static int herdt_check(const zmpc_plan* P, const zmpc_herdt_params* prm, int64_t
   for (int sd = 0; sd < 2; ++sd)
     if (prm->nfacets[sd] < 3 || prm->nfacets[sd] > ZMPC_HERDT_MAX_FACETS)
       return fail(ZMPC_EINVAL, "polytope facets must be in [3, 16]");
-  if (prm->max_footsteps < 0 || prm->max_footsteps > 8)
+  static_assert(kHerdtMaxFootsteps == 8, "the message states the limit");
+  if (prm->max_footsteps < 0 || prm->max_footsteps > kHerdtMaxFootsteps)
     return fail(ZMPC_EINVAL, "max_footsteps must be in [0, 8]");
   if (prm->max_passes < 0 || prm->max_passes > 100000)
     return fail(ZMPC_EINVAL, "max_passes must be in [0, 100000] (0: default)");
@@ -584,36 +585,27 @@ static int herdt_check(const zmpc_plan* P, const zmpc_herdt_params* prm, int64_t
   return ZMPC_OK;
 }
 
-// zmpc_herdt_rollout and, with a push window (kick is NULL then), zmpc_herdt_rollout_pushed
-static int herdt_rollout_impl(const zmpc_plan* P, const zmpc_herdt_params* prm, int64_t B,
-                              int64_t n, const double* v_ref, int64_t v_stride,
-                              const int8_t* states, int64_t s_stride, const int32_t* nb_next,
-                              int64_t nb_stride, const double* x0, const double* kick,
-                              int64_t kick_step, const zmpc_push* push, double* hist, double* foot,
-                              int32_t* status, void* stream) {
-  int rc = herdt_check(P, prm, B);
+// zmpc_herdt_rollout and zmpc_herdt_rollout_pushed: the checks of a filled call, and its launch
+static int herdt_rollout_impl(const zmpc_plan* P, const zmpc_herdt_params* prm, const HerdtCall& c,
+                              void* stream, const char* name) {
+  int rc = herdt_check(P, prm, c.B);
   if (rc != ZMPC_OK) return rc;
-  if (n < 1) return fail(ZMPC_EINVAL, "need n >= 1");
-  if (B == 0) return ZMPC_OK;
-  if (!v_ref || !states || !nb_next || !x0 || !hist || !foot)
+  if (c.n < 1) return fail(ZMPC_EINVAL, "need n >= 1");
+  if (c.B == 0) return ZMPC_OK;
+  if (!c.vref || !c.st || !c.nb || !c.x0 || !c.hist || !c.foot)
     return fail(ZMPC_EINVAL, "NULL array argument");
-  if (B > 0x7fffffff || n > (1 << 24)) return fail(ZMPC_EINVAL, "batch too large");
-  if ((v_stride != 0 && v_stride < 2 * n) || (s_stride != 0 && s_stride < n) ||
-      (nb_stride != 0 && nb_stride < n))
+  if (c.B > 0x7fffffff || c.n > (1 << 24)) return fail(ZMPC_EINVAL, "batch too large");
+  if ((c.vs != 0 && c.vs < 2 * c.n) || (c.ss != 0 && c.ss < c.n) || (c.ns != 0 && c.ns < c.n))
     return fail(ZMPC_EINVAL, "strides must be 0 (shared) or cover a whole walk");
   DeviceGuard g(P->device);
   if (g.err != hipSuccess) return hip_fail(g.err, "hipSetDevice");
   hipStream_t s = (hipStream_t)stream;
-  if (status) {
-    hipError_t e = hipMemsetAsync(status, 0, sizeof(int32_t) * B, s);
+  if (c.status) {
+    hipError_t e = hipMemsetAsync(c.status, 0, sizeof(int32_t) * c.B, s);
     if (e != hipSuccess) return hip_fail(e, "hipMemsetAsync");
   }
   std::string why;
-  hipError_t e = zmpc_launch_herdt(P, prm, B, n, 0, v_ref, v_stride, states, s_stride, nb_next,
-                                   nb_stride, x0, kick, kick_step,
-                                   push ? push_args(push, n) : PushArgs{}, nullptr, nullptr,
-                                   nullptr, hist, foot, status, s, &why);
-  return launch_result(e, why, push ? "zmpc_herdt_rollout_pushed" : "zmpc_herdt_rollout");
+  return launch_result(zmpc_launch_herdt_rollout(P, prm, c, s, &why), why, name);
 }
 
 int zmpc_herdt_rollout(const zmpc_plan* P, const zmpc_herdt_params* prm, int64_t B, int64_t n,
@@ -622,8 +614,9 @@ int zmpc_herdt_rollout(const zmpc_plan* P, const zmpc_herdt_params* prm, int64_t
                        const double* x0, const double* kick, int64_t kick_step, double* hist,
                        double* foot, int32_t* status, void* stream) {
   g_err.clear();
-  return herdt_rollout_impl(P, prm, B, n, v_ref, v_stride, states, s_stride, nb_next, nb_stride,
-                            x0, kick, kick_step, nullptr, hist, foot, status, stream);
+  const HerdtCall c{B, n, v_ref, v_stride, states, s_stride, nb_next, nb_stride, x0, kick,
+                    kick_step, PushArgs{}, hist, foot, status};
+  return herdt_rollout_impl(P, prm, c, stream, "zmpc_herdt_rollout");
 }
 
 int zmpc_herdt_rollout_pushed(const zmpc_plan* P, const zmpc_herdt_params* prm, int64_t B,
@@ -635,11 +628,16 @@ int zmpc_herdt_rollout_pushed(const zmpc_plan* P, const zmpc_herdt_params* prm, 
   if (!P || !prm) return fail(ZMPC_EINVAL, "NULL plan or params");
   const int rc = push_check(push, B);
   if (rc != ZMPC_OK) return rc;
-  if (push_is_kick(push) && !push->steps)  // what users get today
-    return herdt_rollout_impl(P, prm, B, n, v_ref, v_stride, states, s_stride, nb_next, nb_stride,
-                              x0, push->amp, push->step, nullptr, hist, foot, status, stream);
-  return herdt_rollout_impl(P, prm, B, n, v_ref, v_stride, states, s_stride, nb_next, nb_stride,
-                            x0, nullptr, -1, push, hist, foot, status, stream);
+  if (push_is_kick(push) && !push->steps)  // what users get today: zmpc_herdt_rollout's kick
+    return zmpc_herdt_rollout(P, prm, B, n, v_ref, v_stride, states, s_stride, nb_next, nb_stride,
+                              x0, push->amp, push->step, hist, foot, status, stream);
+  HerdtCall c{B, n, v_ref, v_stride, states, s_stride, nb_next, nb_stride, x0};
+  c.kick_step = -1;
+  c.push = push_args(push, n);
+  c.hist = hist;
+  c.foot = foot;
+  c.status = status;
+  return herdt_rollout_impl(P, prm, c, stream, "zmpc_herdt_rollout_pushed");
 }
 
 int zmpc_herdt_walk_metrics(const zmpc_plan* P, const zmpc_herdt_params* prm, int64_t B,
@@ -720,10 +718,9 @@ int zmpc_herdt_step(const zmpc_plan* P, const zmpc_herdt_params* prm, int64_t B,
   DeviceGuard g(P->device);
   if (g.err != hipSuccess) return hip_fail(g.err, "hipSetDevice");
   std::string why;
-  hipError_t e = zmpc_launch_herdt(P, prm, B, 1, 1, v_win, 2 * (int64_t)P->N, s_win, P->N,
-                                   nullptr, 0, x, nullptr, -1, PushArgs{}, current, foot, side,
-                                   x_next, step, status, (hipStream_t)stream, &why);
-  return launch_result(e, why, "zmpc_herdt_step");
+  const HerdtStepCall c{B, x, v_win, s_win, current, foot, side, x_next, step, status};
+  return launch_result(zmpc_launch_herdt_step(P, prm, c, (hipStream_t)stream, &why), why,
+                       "zmpc_herdt_step");
 }
 
 int zmpc_cop_generate(int device, int64_t B, const double* params, int64_t n_cap,

@@ -3,7 +3,7 @@
 // POD structs out; no HIP call, no plan pointer, no environment, no allocation — so that the
 // rules compile and run without a GPU (tests/test_dispatch_host.py pins them).  The launchers
 // (rollout.hip with rollout_long.hip, strict_dispatch.hip, strict_lq.hip, strict_scan.hip,
-// capi.hip) ask here and only launch; the device code reads the layout constants below.
+// herdt.hip, capi.hip) ask here and only launch; the device code reads the layout constants below.
 #pragma once
 
 #include <algorithm>
@@ -489,4 +489,51 @@ inline StrictKind choose_strict(int N, int64_t ninst, int opt_strict_solver, boo
   if (opt_strict_solver == 4) return StrictKind::Scan;  //  only where they run)
   if (scan_ok && (ninst <= kScanMaxInst || !lq_ok)) return StrictKind::Scan;
   return lq_ok ? StrictKind::Lq : StrictKind::Tile;
+}
+
+// ---------------------------------------------------------------------------------------------
+// Herdt joint footstep QP (herdt.hip)
+
+// Most footsteps inside one horizon window (zmpc_herdt_params.max_footsteps), and the footstep
+// capacities MM the kernel is instantiated at: a launch takes the smallest that holds its count.
+constexpr int kHerdtMaxFootsteps = 8;
+constexpr int kHerdtMM[] = {2, 4, 6, 7, 8};
+// facets per swing polygon (ZMPC_HERDT_MAX_FACETS of include/zmpc.h; herdt.hip asserts both)
+constexpr int kHerdtMaxFacets = 16;
+// the swing polygons in LDS (herdt.hip PolyLds): per side and facet 3 doubles of a half-space
+// and 4 of its boundary segment
+constexpr int kHerdtPolyBytes = 2 * kHerdtMaxFacets * (3 + 4) * (int)sizeof(double);
+
+// Dynamic LDS of the kernel's one-wave workgroup at horizon N, byte offsets: per row and lane
+// one byte each of support segment, constraint kind and working-set flag ([N][64] planes), then
+// from a 16-byte boundary the swing polygons, the free-tail feedback ktab [N][4] doubles and the
+// ZMP centres cen [kHerdtMaxFootsteps + 1][64] doubles.  (int: the kernel indexes LDS in 32 bits)
+struct HerdtLds {
+  int segb, kind, wset, poly, ktab, cen, bytes;
+};
+
+constexpr HerdtLds herdt_lds(int N) {
+  HerdtLds l{};
+  l.segb = 0;
+  l.kind = N * 64;
+  l.wset = 2 * N * 64;
+  l.poly = (3 * N * 64 + 15) & ~15;
+  l.ktab = l.poly + kHerdtPolyBytes;
+  l.cen = l.ktab + N * 4 * (int)sizeof(double);
+  l.bytes = l.cen + (kHerdtMaxFootsteps + 1) * 64 * (int)sizeof(double);
+  return l;
+}
+
+// The kernel instance (MM = 0: none, more footsteps than kHerdtMaxFootsteps) and the dynamic LDS
+// of a launch; the launcher refuses lds > kLdsCap (N > 702).
+struct HerdtShape {
+  int MM;
+  size_t lds;
+};
+
+inline HerdtShape herdt_shape(int N, int max_footsteps) {
+  int MM = 0;
+  for (int mm : kHerdtMM)
+    if (MM == 0 && max_footsteps <= mm) MM = mm;
+  return HerdtShape{MM, (size_t)herdt_lds(N).bytes};
 }

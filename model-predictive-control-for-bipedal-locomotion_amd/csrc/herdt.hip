@@ -33,8 +33,6 @@
 // workgroup holds 32 walks.  Sweep 2's rows go through a per-wave global slab ([row][4][64]);
 // per-row segment index, constraint kind and working-set flag are LDS bytes, the swing
 // polygons (half-spaces and facet segments) LDS doubles.
-#include <cstdio>
-#include <cstdlib>
 #include <type_traits>
 
 #include "zmpc_internal.h"
@@ -42,11 +40,6 @@
 namespace {
 
 constexpr int HMAXIT = 64;  // default active-set pass cap (zmpc_herdt_params.max_passes)
-#ifdef ZMPC_DIAG
-constexpr bool kProf = true;  // per-phase clocks (ZMPC_HERDT_PROF), diagnostics build only
-#else
-constexpr bool kProf = false;
-#endif
 
 struct HerdtArgs {
   int N;
@@ -84,8 +77,6 @@ struct HerdtArgs {
   int nf;                // doubles per row in the slab
   unsigned long long* cnt;  // plan work counters [4..7] (zmpc_plan_counters), may be null
   int maxit;                // active-set pass cap per solve (ZMPC_ST_MAXITER beyond)
-  unsigned long long* prof; // diagnostics build only (ZMPC_DIAG, ZMPC_HERDT_PROF): clock per
-                            // phase, summed; null in the product library
   PushArgs push;            // the push window of zmpc_herdt_rollout_pushed; all zero: the kick above
 };
 
@@ -253,6 +244,13 @@ struct RowC {
   double bnd, shi, slo;  // ZMP bounds: foot rows ±bnd around the centre, standing [slo, shi]
 };
 
+// 1/h by the hardware reciprocal + two Newton steps (h > 0)
+__device__ __forceinline__ double rcp_newton(double h) {
+  double iq = __builtin_amdgcn_rcp(h);
+  iq = fma(iq, fma(-h, iq, 1.0), iq);
+  return fma(iq, fma(-h, iq, 1.0), iq);
+}
+
 // One backward Riccati row on V_{k+1}(ξ) = ½ξᵀPξ − sᵀξ → V_k, in place, ξ = [x; f] (NA − 3
 // footstep columns).  Row k's stage cost: ½α u² + ½β(e_vᵀx + b_v u − vr)² + ½γ(c1ᵀx + p0 u −
 // c)² with the ZMP centre c = fc0 (jf < 0) or the footstep f_jf; wk ≠ 0 pins the row's ZMP to
@@ -296,10 +294,8 @@ __device__ __forceinline__ void herdt_row(const RowC& c, double* P, double* s, d
   {
     // both laws, merged by selects: a wave with free and pinned lanes would otherwise run both
     // sides of a branch with its exec-mask bookkeeping, at one wave per SIMD
-    // free: 1/Huu by the hardware reciprocal + two Newton steps (Huu ≥ α + βb_v² + γp0² > 0)
-    double iq = __builtin_amdgcn_rcp(Huu);
-    iq = fma(iq, fma(-Huu, iq, 1.0), iq);
-    iq = fma(iq, fma(-Huu, iq, 1.0), iq);
+    // free: 1/Huu (Huu ≥ α + βb_v² + γp0² > 0)
+    const double iq = rcp_newton(Huu);
     // pinned: c1ᵀx + p0 u − ccon = t  (ccon: the foot centre on a foot row, 0 standing)
     const bool pin = wk != 0, foot = kd == CK_FOOT;
     const double t = (kd == CK_STAND) ? (wk == 1 ? c.shi : c.slo) : (wk == 1 ? c.bnd : -c.bnd);
@@ -393,18 +389,18 @@ __global__ void __launch_bounds__(64) zmpc_herdt_kernel(HerdtArgs a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char hsm[];
   const int lane = threadIdx.x;
   const int N = a.N;
-  unsigned char* segb = hsm;              // [N][64] support segment of row k (0 = current foot)
-  unsigned char* kind = hsm + N * 64;     // [N][64] constraint kind
-  unsigned char* wset = hsm + 2 * N * 64; // [N][64] working set: 0 free, 1 upper, 2 lower
-  PolyLds& pl = *reinterpret_cast<PolyLds*>(hsm + ((3 * N * 64 + 15) & ~15));
-  // free-tail feedback [N][3]: K of row k when rows k..N−1 are all free (it depends on the
-  // working set only; the bounds, v_ref and the centres enter kff)
-  double* ktab = reinterpret_cast<double*>(hsm + ((3 * N * 64 + 15) & ~15) + sizeof(PolyLds));
-  // (ktab row k: K0, K1, K2, 1/Huu; the all-free P after row k is in ptab, global, per
-  // workgroup: sweep 2 starts its full rows from it)
+  const HerdtLds lds = herdt_lds(N);        // the layout, dispatch.h
+  unsigned char* segb = hsm + lds.segb;  // [N][64] support segment of row k (0 = current foot)
+  unsigned char* kind = hsm + lds.kind;  // [N][64] constraint kind
+  unsigned char* wset = hsm + lds.wset;  // [N][64] working set: 0 free, 1 upper, 2 lower
+  PolyLds& pl = *reinterpret_cast<PolyLds*>(hsm + lds.poly);
+  // free-tail feedback [N][4]: K0, K1, K2, 1/Huu of row k when rows k..N−1 are all free (it
+  // depends on the working set only; the bounds, v_ref and the centres enter kff).  The all-free
+  // P after row k is in ptab, global, per workgroup: sweep 2 starts its full rows from it
+  double* ktab = reinterpret_cast<double*>(hsm + lds.ktab);
   // cen [MM+1][64]: the ZMP centre of each support segment after the footstep solve (0: the
   // current foot, j: footstep j) — one LDS read per row instead of a select over MM footsteps
-  double* cen = ktab + N * 4;
+  double* cen = reinterpret_cast<double*>(hsm + lds.cen);
   {
     // both sides' half-spaces and facet segments, once per workgroup
     const int sd = lane >> 5, i = lane & 31;
@@ -447,9 +443,7 @@ __global__ void __launch_bounds__(64) zmpc_herdt_kernel(HerdtArgs a) {
       const double pb1 = Pt[1] * T3 + Pt[3] * T2 + Pt[4] * T;
       const double pb2 = Pt[2] * T3 + Pt[4] * T2 + Pt[5] * T;
       const double Huu = al + be * bv * bv + ga * p0 * p0 + (T3 * pb0 + T2 * pb1 + T * pb2);
-      double iq = __builtin_amdgcn_rcp(Huu);
-      iq = fma(iq, fma(-Huu, iq, 1.0), iq);
-      iq = fma(iq, fma(-Huu, iq, 1.0), iq);
+      const double iq = rcp_newton(Huu);
       herdt_row<3>(rt, Pt, st, 0.0, 0.0, -1, CK_NONE, 0, pbx, sb, Kx, kff);
       if (lane == 0) {
         ktab[k * 4 + 0] = Kx[0];
@@ -490,8 +484,6 @@ __global__ void __launch_bounds__(64) zmpc_herdt_kernel(HerdtArgs a) {
   int fq = 0;
   unsigned long long n_wave_pass = 0, n_pass = 0, n_m = 0, n_m2 = 0;
   unsigned itmax = 0;  // most passes of one solve (counter [9])
-  unsigned long long pr_b = 0, pr_f = 0, pr_w = 0, pr_t0 = (kProf && a.prof) ? clock64() : 0;
-  unsigned long long pr_kw = 0, pr_ns = 0, pr_own = 0, pr_fs = 0, pr_lw = 0;
   const int64_t nsteps = a.window_mode ? 1 : a.n - 1;
   // the lane's push window: steps [kstep, kstep + pdur) (zmpc.h "The push, stated once"; the
   // legacy kick is the window of one step on y)
@@ -568,16 +560,15 @@ __global__ void __launch_bounds__(64) zmpc_herdt_kernel(HerdtArgs a) {
     auto vref = [&](int k) -> double {
       if (a.window_mode) return a.vref[(wc * a.vs / 2 + k) * 2 + axis];
       int64_t t = i + 1 + k;
-      if (t > a.n - 1) t = a.n - 1;
+      if (t > a.n - 1) t = a.n - 1;  // (the same padding)
       return a.vref[wc * a.vs + t * 2 + axis];
     };
 
     double u0 = 0.0, f0 = 0.0;
     int fstep = 0;  // this solve's failure bits (pass cap, infeasible swing polytope)
     double fsol[MM > 0 ? MM : 1];
-    int it = 0, own = 0;  // own: the passes this lane pair needed (diagnostics, ZMPC_HERDT_PROF)
-    bool pair_done = false;
-    bool again = true;  // (itmax: the most passes of one solve, counter [9])
+    int it = 0;
+    bool again = true;
     // Anti-cycling safeguard of the block exchange (Júdice & Pires' block principal pivoting
     // with Murty's least-index fallback): every pass exchanges all wrong rows at once while
     // the count of wrong rows keeps reaching new lows, or for at most PFULL passes in a row
@@ -590,12 +581,10 @@ __global__ void __launch_bounds__(64) zmpc_herdt_kernel(HerdtArgs a) {
     int ninf_best = 0x7fffffff, pfull = PFULL;
     bool single = false;
     while (again) {
-      const unsigned long long tp0 = (kProf && a.prof) ? clock64() : 0;
       // ---- sweep 1: backward Riccati over ξ = [x; f] for V_0(x, f), then the footsteps -----
       // Run at the wave's footstep count (NW = 3 + mw columns, wave-uniform): lanes with fewer
       // footsteps carry zero columns, and no lane pays for the MM − mw columns nobody has.
       double fx0 = 0.0;
-      unsigned long long tp1 = 0, tpf = 0;
       int klane = -1;  // this lane's last pinned row (sweep 1 meets it first)
       auto sweep1 = [&](auto na_tag) {
         constexpr int NW = decltype(na_tag)::value;  // 3 + footstep columns
@@ -625,7 +614,6 @@ __global__ void __launch_bounds__(64) zmpc_herdt_kernel(HerdtArgs a) {
           herdt_row<NW>(rc, P, s, vr, (sg == 0) ? fc : 0.0, sg - 1, kd, wk, pbx, sb, Kx, kff);
           klane = (wk != 0 && klane < 0) ? k : klane;
         }
-        if (kProf && a.prof) tp1 = clock64();
         // ---- footsteps: minimise V_0(x, f) over f, first footstep in the polytope (:771-783)
         double g[MW > 0 ? MW : 1];
 #pragma unroll
@@ -670,7 +658,6 @@ __global__ void __launch_bounds__(64) zmpc_herdt_kernel(HerdtArgs a) {
             if (q < M) fsol[q] = fma(mu, e0[q], gf[q]);
         }
         if (m > 0) fsol[0] = fx0;  // (M = 0: the only footstep lies past the horizon)
-        if (kProf && a.prof) tpf = clock64();
       };
       switch (mw) {
         case 0: sweep1(std::integral_constant<int, 3>{}); break;
@@ -759,7 +746,6 @@ __global__ void __launch_bounds__(64) zmpc_herdt_kernel(HerdtArgs a) {
       // latency of a row's loads.
       bool changed = false;
       int ninf = 0;  // rows of this lane whose working-set flag is wrong after this pass
-      const unsigned long long tp2 = (kProf && a.prof) ? clock64() : 0;
       {
         double xs[3] = {x[0], x[1], x[2]};
         // rows [kb, ke) in blocks of RB; TAIL: K from ktab (rows past the wave's last pinned
@@ -787,12 +773,6 @@ __global__ void __launch_bounds__(64) zmpc_herdt_kernel(HerdtArgs a) {
               sgb[r] = segb[k * 64 + lane];
               kdb[r] = kind[k * 64 + lane];
               wkb[r] = TAIL ? 0 : wset[k * 64 + lane];
-            }
-            if (kProf && a.prof) {
-              // diagnostics: how long the block's loads keep the wave waiting
-              const unsigned long long tw = clock64();
-              __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0) (gfx9 encoding)
-              pr_lw += clock64() - tw;
             }
 #pragma unroll
             for (int r = 0; r < RB; ++r) {
@@ -844,21 +824,6 @@ __global__ void __launch_bounds__(64) zmpc_herdt_kernel(HerdtArgs a) {
         fwd(std::false_type{}, 0, kw + 1);
         fwd(std::true_type{}, kw + 1, N);
       }
-      if (kProf && a.prof) {
-        int kl = -1;
-        for (int k = 0; k < N; ++k)
-          if (wset[k * 64 + lane] != 0) kl = k;
-        for (int o = 32; o > 0; o >>= 1) kl = max(kl, __shfl_xor(kl, o));
-        pr_kw += (unsigned long long)(kl + 1);
-        int nset = 0;
-        for (int k = 0; k < N; ++k) nset += wset[k * 64 + lane] != 0;
-        pr_ns += (unsigned long long)nset;
-        const unsigned long long tp3 = clock64();
-        pr_b += tp1 - tp0;
-        pr_f += tp2 - tp1;
-        pr_fs += tpf - tp1;
-        pr_w += tp3 - tp2;
-      }
       if (ninf == 0) {
         // converged for now, waiting for the wave or the partner axis: start over, so that rows
         // the partner's footstep makes wrong again are exchanged as a block once more
@@ -877,13 +842,6 @@ __global__ void __launch_bounds__(64) zmpc_herdt_kernel(HerdtArgs a) {
       }
       ++it;
       ++n_wave_pass;
-      if (kProf && a.prof) {
-        const bool pch = changed || (__shfl_xor(changed ? 1 : 0, 1, 64) != 0);
-        if (!pair_done) {
-          ++own;
-          pair_done = !pch;
-        }
-      }
       if (valid) {
         ++n_pass;
         n_m += (unsigned)m;
@@ -897,7 +855,6 @@ __global__ void __launch_bounds__(64) zmpc_herdt_kernel(HerdtArgs a) {
       again = __any(changed && valid);
     }
     if (valid) itmax = max(itmax, (unsigned)it);
-    if (valid) pr_own += (unsigned long long)own;
     // an infeasible joint QP (either lane of the pair) — the analogue of OSQP returning no
     // solution — takes the reference's fallback (zmp_controller.py:796-802): zero jerk on both
     // axes and the first footstep at the air foot's centre.  A solve at the pass cap keeps its
@@ -949,34 +906,14 @@ __global__ void __launch_bounds__(64) zmpc_herdt_kernel(HerdtArgs a) {
       h[2] = x[2];
       a.foot[(wc * a.n + i + 1) * 2 + axis] = fc;
     }
-    // warm start: the converged set shifted one row towards the present
-    // (round 3, config 6: row N−1 a copy of the old last row instead of free — 1.316 → 1.157
-    // passes per solve, 86.4 → 78.6 ms; the converged set and the solution do not change)
-    // (row N−1 keeps its value; freeing row N−2 as the strict kernel does changed nothing here,
-    // 1.316 passes either way, and keeping the last 2–3 rows unshifted equals the copy)
+    // warm start: the converged set shifted one row towards the present; row N−1 keeps its value
+    // (a copy of the old last row takes fewer passes per solve than a free row, DESIGN.md §4.5;
+    // the converged set and the solution are the same)
     for (int k = 0; k < N - 1; ++k) wset[k * 64 + lane] = wset[(k + 1) * 64 + lane];
   }
   if (valid && a.status != nullptr) {
     const int other = __shfl(fq, lane ^ 1, 64);
     if (axis == 0) a.status[wc] = fq | other;
-  }
-  if (kProf && a.prof) {
-    for (int o = 32; o > 0; o >>= 1) {
-      pr_ns += __shfl_xor(pr_ns, o);
-      pr_own += __shfl_xor(pr_own, o);
-    }
-    if (lane == 0) {
-      atomicAdd(a.prof + 0, pr_b);
-      atomicAdd(a.prof + 1, pr_f);
-      atomicAdd(a.prof + 2, pr_w);
-      atomicAdd(a.prof + 3, clock64() - pr_t0);
-      atomicAdd(a.prof + 4, pr_kw);
-      atomicAdd(a.prof + 5, pr_ns);
-      atomicAdd(a.prof + 6, n_wave_pass);
-      atomicAdd(a.prof + 7, pr_own);
-      atomicAdd(a.prof + 8, pr_fs);
-      atomicAdd(a.prof + 9, pr_lw);
-    }
   }
   if (a.cnt) {
     for (int o = 32; o > 0; o >>= 1) {
@@ -995,20 +932,33 @@ __global__ void __launch_bounds__(64) zmpc_herdt_kernel(HerdtArgs a) {
   }
 }
 
-}  // namespace
+// The kernel instances, one per footstep capacity of dispatch.h kHerdtMM
+struct HerdtKernel {
+  int MM;
+  void (*fn)(HerdtArgs);
+};
+constexpr HerdtKernel kKernels[] = {{2, zmpc_herdt_kernel<2>},
+                                    {4, zmpc_herdt_kernel<4>},
+                                    {6, zmpc_herdt_kernel<6>},
+                                    {7, zmpc_herdt_kernel<7>},
+                                    {8, zmpc_herdt_kernel<8>}};
+constexpr int kNumKernels = sizeof(kKernels) / sizeof(kKernels[0]);
 
-hipError_t zmpc_launch_herdt(const zmpc_plan* p, const zmpc_herdt_params* prm, int64_t B,
-                             int64_t n, int window_mode, const double* vref, int64_t vs,
-                             const int8_t* st, int64_t ss, const int32_t* nb, int64_t ns,
-                             const double* x0, const double* kick, int64_t kick_step,
-                             const PushArgs& push, const int8_t* cur0, const double* fc0,
-                             const int8_t* side0, double* hist, double* foot, int32_t* status,
-                             hipStream_t s, std::string* why) {
+constexpr bool kernels_match_dispatch() {
+  if (kNumKernels != sizeof(kHerdtMM) / sizeof(kHerdtMM[0])) return false;
+  for (int i = 0; i < kNumKernels; ++i)
+    if (kKernels[i].MM != kHerdtMM[i]) return false;
+  return kKernels[kNumKernels - 1].MM == kHerdtMaxFootsteps;
+}
+static_assert(kernels_match_dispatch(), "kKernels against dispatch.h kHerdtMM");
+static_assert(ZMPC_HERDT_MAX_FACETS == kHerdtMaxFacets && sizeof(PolyLds) == kHerdtPolyBytes,
+              "PolyLds against dispatch.h herdt_lds");
+
+// The plan and parameter part of the kernel arguments, shared by the two calls: LIPM constants,
+// weights, foot sizes, polytopes, pass cap, counters.
+HerdtArgs plan_args(const zmpc_plan* p, const zmpc_herdt_params* prm) {
   HerdtArgs a{};
   a.N = p->N;
-  a.window_mode = window_mode;
-  a.n = n;
-  a.B = B;
   a.T = p->T;
   a.T2 = p->T2_2;
   a.T3 = p->T3_6;
@@ -1027,97 +977,97 @@ hipError_t zmpc_launch_herdt(const zmpc_plan* p, const zmpc_herdt_params* prm, i
   for (int sd = 0; sd < 2; ++sd)
     for (int f = 0; f < ZMPC_HERDT_MAX_FACETS; ++f)
       for (int c = 0; c < 3; ++c) a.poly[sd][f][c] = prm->facets[sd][f][c];
-  a.vref = vref;
-  a.vs = vs;
-  a.st = st;
-  a.ss = ss;
-  a.nb = nb;
-  a.ns = ns;
-  a.x0 = x0;
-  a.kick = kick;
-  a.kick_step = kick_step;
-  a.push = push;
-  a.cur0 = cur0;
-  a.fc0 = fc0;
-  a.side0 = side0;
-  a.hist = hist;
-  a.foot = foot;
-  a.status = status;
   a.cnt = p->lqcnt;
-#ifdef ZMPC_DIAG
-  static unsigned long long* prof = [] {  // diagnostics build: per-phase clocks to stderr
-    unsigned long long* q = nullptr;
-    if (getenv("ZMPC_HERDT_PROF") && hipMalloc((void**)&q, 10 * sizeof(unsigned long long)) != hipSuccess)
-      q = nullptr;
-    return q;
-  }();
-  if (prof) (void)hipMemsetAsync(prof, 0, 10 * sizeof(unsigned long long), s);
-  a.prof = prof;
-#else
-  a.prof = nullptr;
-#endif
   a.maxit = prm->max_passes > 0 ? prm->max_passes : HMAXIT;
-  const int mm = prm->max_footsteps;
-  const int MM = mm <= 2 ? 2 : mm <= 4 ? 4 : mm <= 6 ? 6 : mm <= 7 ? 7 : mm <= 8 ? 8 : 0;
-  if (MM == 0) {
-    *why = "more than 8 footsteps inside one horizon window";
-    return hipErrorInvalidValue;
-  }
   a.nf = SLAB;
-  const int64_t blocks = (B + 31) / 32;
+  return a;
+}
+
+// The launch of filled arguments at the shape dispatch.h herdt_shape gives: the per-wave slab
+// (stream-ordered workspace), the kernel of the shape's MM, the free.
+hipError_t launch(HerdtArgs a, const HerdtShape& shape, hipStream_t s) {
+  const int64_t blocks = (a.B + 31) / 32;
   const size_t slab = (size_t)blocks * a.N * (a.nf * 64 + 6) * sizeof(double);
   if (hipMallocAsync((void**)&a.ws, slab, s) != hipSuccess) {
     (void)hipGetLastError();
     return hipErrorOutOfMemory;
   }
-  const size_t lds = (((size_t)3 * a.N * 64 + 15) & ~(size_t)15) + sizeof(PolyLds) +
-                     (size_t)a.N * 4 * sizeof(double) + (size_t)(8 + 1) * 64 * sizeof(double);
-  if (lds > 160 * 1024) {
-    (void)hipFreeAsync(a.ws, s);
-    *why = "horizon too long for the Herdt solver's LDS flags";
-    return hipErrorInvalidValue;
+  hipError_t e = hipErrorInvalidValue;  // (no instance: the caller refuses such a count first)
+  for (const HerdtKernel& k : kKernels) {
+    if (k.MM != shape.MM) continue;
+    hipLaunchKernelGGL(k.fn, dim3((unsigned)blocks), dim3(64), shape.lds, s, a);
+    e = hipGetLastError();
   }
-  switch (MM) {
-    case 2:
-      hipLaunchKernelGGL(zmpc_herdt_kernel<2>, dim3((unsigned)blocks), dim3(64), lds, s, a);
-      break;
-    case 4:
-      hipLaunchKernelGGL(zmpc_herdt_kernel<4>, dim3((unsigned)blocks), dim3(64), lds, s, a);
-      break;
-    case 6:
-      hipLaunchKernelGGL(zmpc_herdt_kernel<6>, dim3((unsigned)blocks), dim3(64), lds, s, a);
-      break;
-    case 7:
-      hipLaunchKernelGGL(zmpc_herdt_kernel<7>, dim3((unsigned)blocks), dim3(64), lds, s, a);
-      break;
-    default:
-      hipLaunchKernelGGL(zmpc_herdt_kernel<8>, dim3((unsigned)blocks), dim3(64), lds, s, a);
-      break;
-  }
-  hipError_t e = hipGetLastError();
   const hipError_t ef = hipFreeAsync(a.ws, s);
-  if (a.prof && e == hipSuccess) {
-    unsigned long long h[10];
-    (void)hipMemcpy(h, a.prof, sizeof(h), hipMemcpyDeviceToHost);
-    const double t = (double)(h[3] ? h[3] : 1), wp = (double)(h[6] ? h[6] : 1);
-    fprintf(stderr,
-            "herdt prof: backward %.3f footsteps+sweep2 %.3f (footsteps alone %.3f) forward %.3f "
-            "(its slab-load waits %.3f) (of %llu clocks/wave); "
-            "rows to the wave's last pinned row %.1f, pinned rows per lane %.2f (per pass); "
-            "lane-pair passes needed %llu vs wave passes x 64 %llu\n",
-            h[0] / t, h[1] / t, h[8] / t, h[2] / t, h[9] / t, h[3] / (unsigned long long)blocks,
-            h[4] / wp, h[5] / (wp * 64), h[7], h[6] * 64);
-  }
   return e != hipSuccess ? e : ef;
+}
+
+// The shape of a call on plan p, or "none" with the reason in *why
+bool shape_of(const zmpc_plan* p, const zmpc_herdt_params* prm, HerdtShape* shape,
+              std::string* why) {
+  *shape = herdt_shape(p->N, prm->max_footsteps);
+  if (shape->lds <= kLdsCap) return true;
+  *why = "horizon too long for the Herdt solver's LDS flags";
+  return false;
+}
+
+}  // namespace
+
+hipError_t zmpc_launch_herdt_rollout(const zmpc_plan* p, const zmpc_herdt_params* prm,
+                                     const HerdtCall& c, hipStream_t s, std::string* why) {
+  HerdtShape shape;
+  if (!shape_of(p, prm, &shape, why)) return hipErrorInvalidValue;
+  HerdtArgs a = plan_args(p, prm);
+  a.window_mode = 0;
+  a.B = c.B;
+  a.n = c.n;
+  a.vref = c.vref;
+  a.vs = c.vs;
+  a.st = c.st;
+  a.ss = c.ss;
+  a.nb = c.nb;
+  a.ns = c.ns;
+  a.x0 = c.x0;
+  a.kick = c.kick;
+  a.kick_step = c.kick_step;
+  a.push = c.push;
+  a.hist = c.hist;
+  a.foot = c.foot;
+  a.status = c.status;
+  return launch(a, shape, s);
+}
+
+// One step is the kernel's window mode: a walk's inputs are its N-row windows, so the strides are
+// the windows' own (the kernel halves vs there: it counts v_win in rows of 2), and the two output
+// pointers carry x_next [B,2,3] and the first footstep [B,2].
+hipError_t zmpc_launch_herdt_step(const zmpc_plan* p, const zmpc_herdt_params* prm,
+                                  const HerdtStepCall& c, hipStream_t s, std::string* why) {
+  HerdtShape shape;
+  if (!shape_of(p, prm, &shape, why)) return hipErrorInvalidValue;
+  HerdtArgs a = plan_args(p, prm);
+  a.window_mode = 1;
+  a.B = c.B;
+  a.n = 1;
+  a.vref = c.v_win;
+  a.vs = 2 * (int64_t)p->N;
+  a.st = c.s_win;
+  a.ss = p->N;
+  a.x0 = c.x;
+  a.kick_step = -1;
+  a.cur0 = c.current;
+  a.fc0 = c.foot;
+  a.side0 = c.side;
+  a.hist = c.x_next;
+  a.foot = c.step;
+  a.status = c.status;
+  return launch(a, shape, s);
 }
 
 hipError_t zmpc_herdt_set_attrs() {
   hipError_t e = hipSuccess;
-  const void* ks[] = {(const void*)zmpc_herdt_kernel<2>, (const void*)zmpc_herdt_kernel<4>,
-                      (const void*)zmpc_herdt_kernel<6>, (const void*)zmpc_herdt_kernel<7>,
-                      (const void*)zmpc_herdt_kernel<8>};
-  for (const void* k : ks)
+  for (const HerdtKernel& k : kKernels)
     if (e == hipSuccess)
-      e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+      e = hipFuncSetAttribute((const void*)k.fn, hipFuncAttributeMaxDynamicSharedMemorySize,
+                              (int)kLdsCap);
   return e;
 }

@@ -145,6 +145,33 @@ struct StepCall {
   int32_t* status;  // may be null
 };
 
+// The arguments of one zmpc_herdt_rollout / zmpc_herdt_rollout_pushed call.
+struct HerdtCall {
+  int64_t B, n;
+  const double* vref;  // [B,n,2], stride vs doubles per walk (0: one shared [n,2])
+  int64_t vs;
+  const int8_t* st;    // [B,n] support states, stride ss
+  int64_t ss;
+  const int32_t* nb;   // [B,n] steps to the next footstep change, stride ns
+  int64_t ns;
+  const double *x0, *kick;  // kick may be null
+  int64_t kick_step;
+  PushArgs push;       // zmpc_herdt_rollout_pushed: the window (kick is null then); else all zero
+  double *hist, *foot; // [B,n,2,3], [B,n,2]
+  int32_t* status;     // may be null
+};
+
+// The arguments of one zmpc_herdt_step call: windows of the plan's N rows per walk.
+struct HerdtStepCall {
+  int64_t B;
+  const double *x, *v_win;   // [B,2,3], [B,N,2]
+  const int8_t *s_win, *current;  // [B,N], [B]
+  const double* foot;        // [B,2] the current foot
+  const int8_t* side;        // [B] its side (0 left)
+  double *x_next, *step;     // [B,2,3]; [B,2] the first footstep (NaN without one in the window)
+  int32_t* status;           // may be null
+};
+
 // kernels launchers (plan.hip); ev (may be NULL): ZMPC_PLAN_STAGES events, ev[0] recorded
 // before the first stage and ev[i + 1] after stage i for stages 0..9 of include/zmpc.h
 // zmpc_plan_timings (stages the plan skips record their event right after the previous one);
@@ -275,13 +302,10 @@ hipError_t zmpc_kick_order(const double* kick, const int64_t* kick_steps, int64_
 
 // Herdt joint footstep QP (herdt.hip); support states as cop_generator.State
 constexpr int ZMPC_STANDING = 0, ZMPC_DOUBLE_SUPPORT = 1, ZMPC_SINGLE_SUPPORT = 2;
-hipError_t zmpc_launch_herdt(const zmpc_plan* p, const zmpc_herdt_params* prm, int64_t B,
-                             int64_t n, int window_mode, const double* vref, int64_t vs,
-                             const int8_t* st, int64_t ss, const int32_t* nb, int64_t ns,
-                             const double* x0, const double* kick, int64_t kick_step,
-                             const PushArgs& push, const int8_t* cur0, const double* fc0,
-                             const int8_t* side0, double* hist, double* foot, int32_t* status,
-                             hipStream_t s, std::string* why);
+hipError_t zmpc_launch_herdt_rollout(const zmpc_plan* p, const zmpc_herdt_params* prm,
+                                     const HerdtCall& c, hipStream_t s, std::string* why);
+hipError_t zmpc_launch_herdt_step(const zmpc_plan* p, const zmpc_herdt_params* prm,
+                                  const HerdtStepCall& c, hipStream_t s, std::string* why);
 hipError_t zmpc_herdt_set_attrs();
 
 hipError_t zmpc_rollout_unc_set_attrs();

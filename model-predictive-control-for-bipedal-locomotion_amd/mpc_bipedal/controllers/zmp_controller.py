@@ -48,6 +48,45 @@ def _default_force_step(n, lengths):
     return n // 2 if lengths is None else lengths // 2
 
 
+def _force_step(force_step, n, lengths):
+    """The force_step argument of the critical-force searches: None gives the default above, a
+    scalar an int, a [B] argument stays as given."""
+    if force_step is None:
+        return _default_force_step(n, lengths)
+    return int(force_step) if np.ndim(force_step) == 0 else force_step
+
+
+def _unit_push(direction, unit, B):
+    """One newton along each scenario's direction, as analysis.Push takes it: (F1 [B], d1 [B,2])
+    host arrays whose amplitudes a bisection scales.  unit: planar unit vectors [1, 2] or [B, 2],
+    broadcast; else direction holds a sign or [B] signs on the host, pushed along y, and a sign
+    of 0 is no push, through a zero force."""
+    if unit is not None:
+        return np.ones(B), np.broadcast_to(unit, (B, 2))
+    sign = np.sign(np.broadcast_to(np.asarray(direction, np.float64), (B,)))
+    return np.abs(sign), np.stack([np.zeros(B), np.where(sign == 0, 1.0, sign)], axis=1)
+
+
+def _bisect(passes, B, F_hi, iters, f64, after_unpushed=None):
+    """The bracket of critical_force and critical_force_herdt: passes(F [B]) -> [B] bool runs one
+    evaluation; the unpushed one comes first (after_unpushed() is called behind it), then the top
+    of the bracket, then iters halvings: iters + 2 evaluations.  Returns (F_lo, F_hi), NaN in both
+    where the unpushed walk fails."""
+    top = torch.full((B,), float(F_hi), **f64)
+    lo = torch.zeros(B, **f64)
+    hi = top.clone()
+    never = ~passes(lo)
+    if after_unpushed is not None:
+        after_unpushed()
+    lo = torch.where(passes(top), top, lo)
+    for _ in range(int(iters)):
+        mid = 0.5 * (lo + hi)
+        ok = passes(mid)
+        lo, hi = torch.where(ok, mid, lo), torch.where(ok, hi, mid)
+    nan = torch.full_like(lo, float("nan"))
+    return torch.where(never, nan, lo), torch.where(never, nan, hi)
+
+
 def _direction_size(direction, unit):
     """direction as an argument that sizes the scenario batch (_scenario's `sized`): a sign or
     [B] signs as given; planar directions (unit [K, 2], else None) count as a [K] argument when
@@ -512,22 +551,13 @@ class ZMPController:
             sign = None
         else:
             sign = torch.sign(torch.as_tensor(direction, **f64)).expand(B).contiguous()
-        if force_step is None:
-            step = _default_force_step(n, lengths)
-        elif np.ndim(force_step) == 0:
-            step = int(force_step)
-        else:
-            step = torch.as_tensor(force_step, dtype=torch.int64, device=dev)
+        step = _force_step(force_step, n, lengths)
+        if not isinstance(step, int):
+            step = torch.as_tensor(step, dtype=torch.int64, device=dev)
         kick = torch.zeros(B, **f64)
         metrics = torch.empty((B, NMETRICS), **f64)
         if shove:
-            # one newton along each scenario's direction; the bisection scales the amplitudes
-            if planar:
-                d1 = np.broadcast_to(unit, (B, 2))
-            else:
-                d1 = np.stack([np.zeros(B), sign.cpu().numpy()], axis=1)
-                d1[d1[:, 1] == 0, 1] = 1.0  # (sign 0: no push, through a zero force below)
-            F1 = np.ones(B) if planar else np.abs(sign.cpu().numpy())
+            F1, d1 = _unit_push(None if planar else sign.cpu().numpy(), unit, B)
             st = step.cpu().numpy() if isinstance(step, torch.Tensor) else step
             push = Push(F1, d1, st, duration=D, profile=w)
             launch = plan.rollout_launcher(zmax_t, zmin_t, x0, push=push, mass=self.config.m)
@@ -557,17 +587,7 @@ class ZMPController:
                 ok &= launch.status == 0
             return ok
 
-        top = torch.full((B,), float(F_hi), **f64)
-        lo = torch.zeros(B, **f64)
-        hi = top.clone()
-        never = ~passes(lo)
-        lo = torch.where(passes(top), top, lo)
-        for _ in range(int(iters)):
-            mid = 0.5 * (lo + hi)
-            ok = passes(mid)
-            lo, hi = torch.where(ok, mid, lo), torch.where(ok, hi, mid)
-        nan = torch.full_like(lo, float("nan"))
-        return torch.where(never, nan, lo), torch.where(never, nan, hi)
+        return _bisect(passes, B, F_hi, iters, f64)
 
     # ------------------------------------------------------------------ Herdt robustness
     def herdt_walk_metrics(self, hist, foot, state_ref, foot_ref=None,
@@ -657,20 +677,13 @@ class ZMPController:
             raise ValueError(f"force_step and direction must be scalars or [B] = [{B}] (planar "
                              "directions [1, 2] or [B, 2])")
         x0 = torch.zeros((B, 2, 3), **f64) if x_init is None else torch.as_tensor(x_init, **f64)
-        if force_step is None:
-            step = _default_force_step(n, None if walk_lengths is None else
-                                       self._lengths_host(walk_lengths, B, n))
-        elif np.ndim(force_step) == 0:
-            step = int(force_step)
-        else:
-            step = np.asarray(torch.as_tensor(force_step).cpu(), np.int64)
-        # one newton along each scenario's direction; the bisection scales the amplitudes
-        if planar:
-            d1, F1 = np.broadcast_to(unit, (B, 2)), np.ones(B)
-        else:
-            sign = np.sign(np.broadcast_to(np.asarray(direction, np.float64), (B,)))
-            d1 = np.stack([np.zeros(B), np.where(sign == 0, 1.0, sign)], axis=1)
-            F1 = np.abs(sign)  # (sign 0: no push, through a zero force)
+        lengths = None
+        if force_step is None and walk_lengths is not None:
+            lengths = self._lengths_host(walk_lengths, B, n)
+        step = _force_step(force_step, n, lengths)
+        if not isinstance(step, int):
+            step = np.asarray(torch.as_tensor(step).cpu(), np.int64)
+        F1, d1 = _unit_push(direction, unit, B)
         prm, st, nb, v = self._herdt_device(plan, st, v, walk_lengths)
         launch = plan.herdt_rollout_launcher(prm, v, st, nb, x0,
                                              Push(F1, d1, step, duration=D, profile=w),
@@ -678,33 +691,28 @@ class ZMPController:
         amp1 = launch.push_amp.clone()  # [B, C] for 1 N
         metrics = torch.empty((B, NHERDT_METRICS), **f64)
         foot_ref = torch.empty_like(launch.foot)
-        measure0, measure = (plan.herdt_walk_metrics_launcher(
+        measure, measure_ref = (plan.herdt_walk_metrics_launcher(
             prm, launch.hist, launch.foot, launch.states, lengths=walk_lengths, foot_ref=ref,
             count_tol=max_violation, out=metrics) for ref in (None, foot_ref))
         m = HerdtWalkMetrics(metrics)
 
-        def passes(F, first=False):
+        def passes(F):
             launch.push_amp.copy_(amp1 * F[:, None])
             launch()
-            (measure0 if first else measure)()
+            measure()
             ok = (m.viol_max <= max_violation).all(dim=1)  # (+inf and NaN fail)
             ok &= (m.dcm_dev_max <= max_dcm_dev).all(dim=1)
             if max_com_dev is not None:
                 ok &= (m.com_dev_max <= max_com_dev).all(dim=1)
             return ok & (launch.status == 0)
 
-        top = torch.full((B,), float(F_hi), **f64)
-        lo = torch.zeros(B, **f64)
-        hi = top.clone()
-        never = ~passes(lo, first=True)
-        foot_ref.copy_(launch.foot)
-        lo = torch.where(passes(top), top, lo)
-        for _ in range(int(iters)):
-            mid = 0.5 * (lo + hi)
-            ok = passes(mid)
-            lo, hi = torch.where(ok, mid, lo), torch.where(ok, hi, mid)
-        nan = torch.full_like(lo, float("nan"))
-        return torch.where(never, nan, lo), torch.where(never, nan, hi)
+        def keep_unpushed_feet():
+            # the unpushed walk's feet are the foot_ref of every later evaluation
+            nonlocal measure
+            foot_ref.copy_(launch.foot)
+            measure = measure_ref
+
+        return _bisect(passes, B, F_hi, iters, f64, after_unpushed=keep_unpushed_feet)
 
     def _unpushed(self, z_max, z_min, x_init, walk_lengths, extra=()):
         """One unpushed rollout for the push map: (plan, hist, zmax, zmin, lengths, B, n)."""

@@ -6,6 +6,7 @@
 //   strict N ninst opt_strict_solver has_lq_table -> kind
 //   scan N ninst cus                       -> lanes C
 //   caps                                   -> wide_lds_cap(2) wide_lds_cap(4) wide_lds_cap(8)
+//   herdt N max_footsteps                  -> MM lds fits(lds <= kLdsCap) poly ktab cen
 #include <cstdio>
 #include <cstring>
 
@@ -18,7 +19,8 @@ int main() {
   long long a[6];
   while (scanf("%15s", tag) == 1) {
     const int want = !strcmp(tag, "unc") ? 6 : !strcmp(tag, "lq") ? 1 : !strcmp(tag, "strict") ? 4
-                     : !strcmp(tag, "scan") ? 3 : !strcmp(tag, "caps") ? 0 : -1;
+                     : !strcmp(tag, "scan") ? 3 : !strcmp(tag, "caps") ? 0
+                     : !strcmp(tag, "herdt") ? 2 : -1;
     if (want < 0) return 2;
     for (int i = 0; i < want; ++i)
       if (scanf("%lld", &a[i]) != 1) return 2;
@@ -34,6 +36,10 @@ int main() {
     } else if (!strcmp(tag, "scan")) {
       const ScanShape s = scan_shape((int)a[0], a[1], (int)a[2]);
       printf("%d %d\n", s.lanes, s.C);
+    } else if (!strcmp(tag, "herdt")) {
+      const HerdtShape s = herdt_shape((int)a[0], (int)a[1]);
+      const HerdtLds l = herdt_lds((int)a[0]);
+      printf("%d %zu %d %d %d %d\n", s.MM, s.lds, (int)(s.lds <= kLdsCap), l.poly, l.ktab, l.cen);
     } else {
       printf("%zu %zu %zu\n", wide_lds_cap(2), wide_lds_cap(4), wide_lds_cap(8));
     }

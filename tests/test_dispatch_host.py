@@ -104,6 +104,21 @@ SCAN = (
     ((64, 131072, 256), (32, 2)),
 )
 
+# The Herdt kernel (generated from herdt.hip's launcher and kernel as they stood before the rule
+# moved into dispatch.h: the instance choice, the LDS byte formula and the kernel's pointer
+# arithmetic cut out unchanged, with ZMPC_HERDT_MAX_FACETS = 16).
+# N -> (dynamic LDS bytes = 224 N + 6400, within the 160 KiB limit, byte offsets of the swing
+# polygons, the free-tail table and the ZMP centres behind the three [N][64] byte planes)
+HERDT_LDS = (
+    (1, (6624, 1, 192, 1984, 2016)),
+    (33, (13792, 1, 6336, 8128, 9184)),
+    (150, (40000, 1, 28800, 30592, 35392)),
+    (702, (163648, 1, 134784, 136576, 159040)),   # the last horizon that fits
+    (703, (163872, 0, 134976, 136768, 159264)),   # refused
+)
+# max_footsteps -> the kernel instance MM (0: none)
+HERDT_MM = ((0, 2), (1, 2), (2, 2), (3, 4), (4, 4), (5, 6), (6, 6), (7, 7), (8, 8), (9, 0))
+
 
 @pytest.fixture(scope="module")
 def ask(tmp_path_factory):
@@ -149,6 +164,13 @@ def test_strict_choices(ask):
 def test_scan_shapes(ask):
     got = ask("scan", [q for q, _ in SCAN])
     for (q, want), g in zip(SCAN, got):
+        assert g == want, (q, g)
+
+
+def test_herdt_shapes(ask):
+    queries = [(n, mf) for n, _ in HERDT_LDS for mf, _ in HERDT_MM]
+    wants = [(mm,) + lds for _, lds in HERDT_LDS for _, mm in HERDT_MM]
+    for q, want, g in zip(queries, wants, ask("herdt", queries)):
         assert g == want, (q, g)
 
 
