@@ -43,7 +43,9 @@ extern "C" {
 
 /* per-instance status flags (bitwise OR) */
 #define ZMPC_ST_MAXITER 1  /* strict active-set iteration cap reached */
-#define ZMPC_ST_NONFINITE 2 /* a non-finite value was produced */
+#define ZMPC_ST_NONFINITE 2 /* a non-finite value was produced (unconstrained walks of more than
+                               513 samples: also a non-finite bound at sample 0, which no
+                               window reads) */
 #define ZMPC_ST_FACTOR 4   /* reduced KKT matrix not positive definite (Herdt: also a
                               window with more footsteps than params.max_footsteps, flagged
                               on every walk of its 32-walk wave) */

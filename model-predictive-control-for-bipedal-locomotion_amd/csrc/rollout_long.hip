@@ -529,9 +529,17 @@ __global__ void __launch_bounds__(128 * W, E == 4 ? 6 : 4) zmpc_rollout_unc_wide
     const bool finite = isfinite(x[0]) && isfinite(x[1]) && isfinite(x[2]);
     const unsigned long long bad = __ballot(!finite);
     if (lane == 0) flag[wv] = bad ? ZMPC_ST_NONFINITE : 0;
+    // Sample 0 of the bounds has weight zero in every window: the direct form never reads it,
+    // the sparse and FFT forms turn a non-finite one into a non-finite walk.  The status flags
+    // it under every form (loads issued ahead of the barrier).
+    double2 h0 = make_double2(0.0, 0.0), l0 = h0;
+    if (tid == 0) {
+      h0 = *reinterpret_cast<const double2*>(a.zmax + b * a.bstride);
+      l0 = *reinterpret_cast<const double2*>(a.zmin + b * a.bstride);
+    }
     __syncthreads();
     if (tid == 0) {
-      int fl = 0;
+      int fl = (isfinite(h0.x + l0.x) && isfinite(h0.y + l0.y)) ? 0 : ZMPC_ST_NONFINITE;
       for (int v = 0; v < 2 * W; ++v) fl |= flag[v];
       a.status[b] = fl;
     }
@@ -707,8 +715,11 @@ __global__ void __launch_bounds__(64) zmpc_rollout_unc_chunk_kernel(RolloutArgs 
     chunk_scan_replay<CW>(a, lane, f0, f1, zr0, rows_pr, xs, ys, kk, kstep, t0, ns, hb);
   }
   if (a.status != nullptr) {
+    // (sample 0 of the bounds, which no window reads, is flagged as the wide kernel flags it)
+    const double2 h0 = zmx[0], l0 = zmn[0];
     const bool finite = isfinite(xs[0]) && isfinite(xs[1]) && isfinite(xs[2]) &&
-                        isfinite(ys[0]) && isfinite(ys[1]) && isfinite(ys[2]);
+                        isfinite(ys[0]) && isfinite(ys[1]) && isfinite(ys[2]) &&
+                        isfinite(h0.x + l0.x) && isfinite(h0.y + l0.y);
     if (lane == 0) a.status[b] = finite ? 0 : ZMPC_ST_NONFINITE;
   }
 }
