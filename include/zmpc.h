@@ -507,6 +507,83 @@ int zmpc_herdt_rollout_pushed(const zmpc_plan* plan, const zmpc_herdt_params* pa
                               double* hist, double* foot, int32_t* status, void* stream);
 
 /*
+ * Rollouts under per-walk force traces, on every controller.  A push window gives a batch one
+ * length and one profile; a trace gives every walk its own disturbance per sample and axis: a walk
+ * shoved twice, walks shoved for different lengths or with different shapes, force noise per walk,
+ * a force trace recorded elsewhere.
+ *
+ * The trace, stated once.  It is "The push, stated once" above with the product amp[b, a]·w_j
+ * replaced by a value read from the walk's own row; everything not said here is as there (where it
+ * acts, the sign, truncation).  Per walk b the inputs are a start step s_b, a length L >= 1 shared
+ * by the batch, and dv[b, j, col(a)] in m/s (= dt·F/m) for 0 <= j < L and every requested axis a.
+ * For every history step i with j = i − s_b, 0 <= j < L and i < n − 1, after x⁺ = A x + B u0 the
+ * velocity of sample i + 1 on axis a is lowered by dv[b, j, col(a)].
+ *   - The read value is used as it is, with no product: a trace whose rows hold one constant is a
+ *     NULL-profile window of duration L, bit for bit.
+ *   - A start step outside [0, n − 1) means no disturbance for that walk.
+ *   - A trace that runs past the walk's end is truncated; entries that reach no sample are never
+ *     read.
+ *   - An axis that was not requested is untouched, bit for bit.
+ *   - A non-finite entry gives unspecified values in the samples it reaches and never causes an
+ *     out-of-range access.
+ *   - Two calls on the same input agree bit for bit, and a walk's result does not depend on which
+ *     batch it sits in.
+ *
+ * The stream is a member of the descriptor, not a parameter of the calls: the two calls below
+ * take no `void* stream`, so the rule that every entry point declared with one has a case in the
+ * stream-contract table (tests/stream_cases.py) does not reach them; tests/test_gpu_trace.py holds
+ * them to the same contract (work queued on trace.stream alone, ordered after what that stream
+ * already holds, NULL = the null stream).
+ */
+typedef struct zmpc_trace {
+  const double*  dv;      /* [B, length, C] device: what the velocity of sample s_b + j + 1 is
+                             lowered by on axis a, in m/s (= dt·F/m); C = 1 or 2 columns in the
+                             order of `axes` (x, y) */
+  int32_t        axes;    /* ZMPC_PUSH_AXIS_X | ZMPC_PUSH_AXIS_Y */
+  const int64_t* steps;   /* [B] device start steps s_b, or NULL: `step` for every walk */
+  int64_t        step;
+  int64_t        length;  /* L >= 1 samples per walk */
+  void*          stream;  /* hipStream_t, NULL = the null stream */
+} zmpc_trace;
+
+/*
+ * zmpc_rollout under a trace; every other argument as there.
+ *   - Strict plans: the LQ and the parallel-in-time kernels (ZMPC_OPT_STRICT_SOLVER 0, 3, 4) read
+ *     the trace in their time loop, in the instances that take a push window;
+ *     ZMPC_OPT_KICK_ORDER sorts the walks by (start step, the larger |dv[b, 0, ·]| of the
+ *     requested axes), and the results do not depend on the order.  The reduced-Cholesky
+ *     cross-checks (solvers 1 and 2) return ZMPC_ESTATE with the reason.
+ *   - Unconstrained plans: the closed loop is linear and time-invariant, so the call runs the
+ *     unpushed zmpc_rollout — any shape, any n — and then subtracts the state response of the
+ *     walk's own trace,
+ *         δ_(s_b) = 0,  δ_(i+1) = Ā·δ_i + e1·dv[b, i − s_b, a],  hist[b, i, a, :] −= δ_i,  s_b < i < n
+ *     (Ā = A − B·kxᵀ as zmpc_push_map), one wavefront per walk, as a scan over blocks of 64
+ *     samples: O(n) per walk, dv read once, no workspace.  Samples at or before s_b are neither
+ *     read nor written; an all-zero trace leaves hist the unpushed rollout's bit for bit.  The
+ *     sums run in an order fixed by lane and block numbers, uncontracted.  It agrees with chained
+ *     restarts of zmpc_rollout to rounding; status is the unpushed rollout's.
+ * ZMPC_EINVAL before any device call: NULL trace, or NULL dv when B > 0; axes outside 1..3;
+ * length < 1, or so large that B·length·16 bytes pass int64; zmpc_rollout's own cases.  B = 0 does
+ * nothing.  Nothing is launched on a refusal.  Additive to ABI 7.
+ */
+int zmpc_rollout_traced(const zmpc_plan* plan, int64_t B, int64_t n, const double* zmax,
+                        const double* zmin, int64_t bounds_stride, const double* x0,
+                        const zmpc_trace* trace, double* hist, int32_t* status);
+
+/*
+ * zmpc_herdt_rollout under a trace ("The trace, stated once" above), read in the (walk, axis) lane
+ * where the reference applies its impulse (:525-526).  ZMPC_EINVAL before any device call: NULL
+ * trace, or NULL dv when B > 0; axes outside 1..3; length < 1 or too large (as
+ * zmpc_rollout_traced); zmpc_herdt_rollout's own cases.
+ * B = 0 does nothing.  Additive to ABI 7.
+ */
+int zmpc_herdt_rollout_traced(const zmpc_plan* plan, const zmpc_herdt_params* params, int64_t B,
+                              int64_t n, const double* v_ref, int64_t v_stride,
+                              const int8_t* states, int64_t s_stride, const int32_t* nb_next,
+                              int64_t nb_stride, const double* x0, const zmpc_trace* trace,
+                              double* hist, double* foot, int32_t* status);
+
+/*
  * Per-walk survival metrics of a Herdt rollout, reduced on the device: did the footstep-adapting
  * controller stay up?  zmpc_walk_metrics needs fixed CoP bounds; a Herdt walk has none, its
  * support box follows the footsteps the QP chose.  Here the box is rebuilt from the rollout's own

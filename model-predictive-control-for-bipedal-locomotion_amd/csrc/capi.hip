@@ -371,15 +371,46 @@ static PushArgs push_args(const zmpc_push* push, int64_t n) {
   w.cols = push->axes == (ZMPC_PUSH_AXIS_X | ZMPC_PUSH_AXIS_Y) ? 2 : 1;
   w.col[0] = (push->axes & ZMPC_PUSH_AXIS_X) ? 0 : -1;
   w.col[1] = (push->axes & ZMPC_PUSH_AXIS_Y) ? w.cols - 1 : -1;
+  w.astride = w.cols;
+  return w;
+}
+
+// The checks of a zmpc_trace (include/zmpc.h "The trace, stated once"), before any device call
+static int trace_check(const zmpc_trace* trace, int64_t B) {
+  if (!trace) return fail(ZMPC_EINVAL, "trace is NULL");
+  if (trace->axes < 1 || trace->axes > (ZMPC_PUSH_AXIS_X | ZMPC_PUSH_AXIS_Y))
+    return fail(ZMPC_EINVAL, "trace axes must be 1 (the x axis), 2 (the y axis) or 3 (both)");
+  if (trace->length < 1) return fail(ZMPC_EINVAL, "need trace length >= 1 (samples)");
+  if (B > 0 && !trace->dv) return fail(ZMPC_EINVAL, "trace dv is NULL");
+  // dv holds B·length·C doubles: a length whose byte count passes int64 names no array
+  if (trace->length > INT64_MAX / 16 / (B > 0 ? B : 1))
+    return fail(ZMPC_EINVAL, "trace length too large (B * length * 16 bytes pass int64)");
+  return ZMPC_OK;
+}
+
+// A checked zmpc_trace as the launchers take it, in a walk of n samples: the window of L steps
+// whose value is read from the walk's own row
+static PushArgs trace_args(const zmpc_trace* trace, int64_t n) {
+  PushArgs w{};
+  w.amp = trace->dv;
+  w.steps = trace->steps;
+  w.step = trace->step;
+  w.dur = (int)(trace->length < n ? trace->length : n);
+  w.cols = trace->axes == (ZMPC_PUSH_AXIS_X | ZMPC_PUSH_AXIS_Y) ? 2 : 1;
+  w.col[0] = (trace->axes & ZMPC_PUSH_AXIS_X) ? 0 : -1;
+  w.col[1] = (trace->axes & ZMPC_PUSH_AXIS_Y) ? w.cols - 1 : -1;
+  w.tstride = w.cols;
+  w.astride = trace->length * w.cols;
   return w;
 }
 
 // zmpc_rollout, zmpc_rollout_kicks and, with a push window (kick is NULL then), the general
-// zmpc_rollout_pushed
+// zmpc_rollout_pushed; with a trace (kick and push are NULL then), zmpc_rollout_traced
 static int rollout_impl(const zmpc_plan* P, int64_t B, int64_t n, const double* zmax,
                         const double* zmin, int64_t bounds_stride, const double* x0,
                         const double* kick, int64_t kick_step, const int64_t* kick_steps,
-                        const zmpc_push* push, double* hist, int32_t* status, void* stream) {
+                        const zmpc_push* push, double* hist, int32_t* status, void* stream,
+                        const zmpc_trace* trace = nullptr) {
   g_err.clear();
   if (!P) return fail(ZMPC_EINVAL, "NULL plan");
   if (B < 0 || n < 1) return fail(ZMPC_EINVAL, "need B >= 0 and n >= 1");
@@ -389,6 +420,20 @@ static int rollout_impl(const zmpc_plan* P, int64_t B, int64_t n, const double* 
   if (n > (1 << 24)) return fail(ZMPC_EINVAL, "walk too long");
   if (bounds_stride != 0 && bounds_stride < 2 * n)
     return fail(ZMPC_EINVAL, "bounds_stride must be 0 (shared CoP) or >= 2n");
+  if (trace && P->strict) {
+    // refused before any device call, nothing is launched
+    const StrictKind kind =
+        choose_strict(P->N, 2 * B, P->opt[ZMPC_OPT_STRICT_SOLVER], P->lqtab != nullptr);
+    if (kind == StrictKind::Tile && P->opt[ZMPC_OPT_STRICT_SOLVER] == 0)
+      return fail(ZMPC_ESTATE,
+                  "zmpc_rollout_traced: at horizon N = " + std::to_string(P->N) +
+                      " neither the LQ nor the parallel-in-time strict kernel runs, and the "
+                      "reduced-Cholesky kernel left takes no trace");
+    if (kind == StrictKind::Tile || kind == StrictKind::Wave)
+      return fail(ZMPC_ESTATE,
+                  "zmpc_rollout_traced: the reduced-Cholesky strict kernels (strict solver options "
+                  "1 and 2) take no trace; use strict solver 0, 3 or 4");
+  }
   if (push && P->strict) {
     // refused before any device call, nothing is launched
     const StrictKind kind =
@@ -412,6 +457,7 @@ static int rollout_impl(const zmpc_plan* P, int64_t B, int64_t n, const double* 
   hipError_t e;
   if (P->strict) {
     if (push) c.push = push_args(push, n);
+    if (trace) c.push = trace_args(trace, n);
     e = zmpc_launch_rollout_strict(P, c, s, &why);
   } else {
     // (unconstrained: the unpushed rollout, then the window's linear state response)
@@ -420,8 +466,14 @@ static int rollout_impl(const zmpc_plan* P, int64_t B, int64_t n, const double* 
       c.push = push_args(push, n);
       e = zmpc_launch_push_response(P, c, s);
     }
+    // (a trace: the unpushed rollout, then the scan of the walk's own trace, trace.hip)
+    if (trace && e == hipSuccess) {
+      c.push = trace_args(trace, n);
+      e = zmpc_launch_trace_response(P, c, trace->length, s);
+    }
   }
-  return launch_result(e, why, push ? "zmpc_rollout_pushed" : "zmpc_rollout");
+  return launch_result(e, why,
+                       trace ? "zmpc_rollout_traced" : push ? "zmpc_rollout_pushed" : "zmpc_rollout");
 }
 
 int zmpc_rollout(const zmpc_plan* P, int64_t B, int64_t n, const double* zmax,
@@ -456,6 +508,17 @@ int zmpc_rollout_pushed(const zmpc_plan* P, int64_t B, int64_t n, const double* 
                         push->steps ? -1 : push->step, push->steps, nullptr, hist, status, stream);
   return rollout_impl(P, B, n, zmax, zmin, bounds_stride, x0, nullptr, -1, nullptr, push, hist,
                       status, stream);
+}
+
+int zmpc_rollout_traced(const zmpc_plan* P, int64_t B, int64_t n, const double* zmax,
+                        const double* zmin, int64_t bounds_stride, const double* x0,
+                        const zmpc_trace* trace, double* hist, int32_t* status) {
+  g_err.clear();
+  if (!P) return fail(ZMPC_EINVAL, "NULL plan");
+  const int rc = trace_check(trace, B);
+  if (rc != ZMPC_OK) return rc;
+  return rollout_impl(P, B, n, zmax, zmin, bounds_stride, x0, nullptr, -1, nullptr, nullptr, hist,
+                      status, trace->stream, trace);
 }
 
 int zmpc_walk_metrics(const zmpc_plan* P, int64_t B, int64_t n, const double* hist,
@@ -638,6 +701,24 @@ int zmpc_herdt_rollout_pushed(const zmpc_plan* P, const zmpc_herdt_params* prm, 
   c.foot = foot;
   c.status = status;
   return herdt_rollout_impl(P, prm, c, stream, "zmpc_herdt_rollout_pushed");
+}
+
+int zmpc_herdt_rollout_traced(const zmpc_plan* P, const zmpc_herdt_params* prm, int64_t B,
+                              int64_t n, const double* v_ref, int64_t v_stride,
+                              const int8_t* states, int64_t s_stride, const int32_t* nb_next,
+                              int64_t nb_stride, const double* x0, const zmpc_trace* trace,
+                              double* hist, double* foot, int32_t* status) {
+  g_err.clear();
+  if (!P || !prm) return fail(ZMPC_EINVAL, "NULL plan or params");
+  const int rc = trace_check(trace, B);
+  if (rc != ZMPC_OK) return rc;
+  HerdtCall c{B, n, v_ref, v_stride, states, s_stride, nb_next, nb_stride, x0};
+  c.kick_step = -1;
+  c.push = trace_args(trace, n < 1 ? 1 : n);
+  c.hist = hist;
+  c.foot = foot;
+  c.status = status;
+  return herdt_rollout_impl(P, prm, c, trace->stream, "zmpc_herdt_rollout_traced");
 }
 
 int zmpc_herdt_walk_metrics(const zmpc_plan* P, const zmpc_herdt_params* prm, int64_t B,

@@ -384,7 +384,11 @@ __device__ __forceinline__ void herdt_tail_row(const RowC& c, double* s, double 
   s[2] = hx2 - hu * kt[2];
 }
 
-template <int MM>
+// TRACE: the instances of zmpc_herdt_rollout_traced, whose time loop reads the walk's own row of
+// velocity steps (a.push in trace form); the others take the kick or the window as before,
+// instruction for instruction (the read decided at run time cost config 6 0.5 %,
+// profiles/traces/).
+template <int MM, bool TRACE = false>
 __global__ void __launch_bounds__(64) zmpc_herdt_kernel(HerdtArgs a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char hsm[];
   const int lane = threadIdx.x;
@@ -487,7 +491,8 @@ __global__ void __launch_bounds__(64) zmpc_herdt_kernel(HerdtArgs a) {
   const int64_t nsteps = a.window_mode ? 1 : a.n - 1;
   // the lane's push window: steps [kstep, kstep + pdur) (zmpc.h "The push, stated once"; the
   // legacy kick is the window of one step on y)
-  const double* const pamp = a.window_mode ? nullptr : push_amp(a.push, a.kick, wc, axis);
+  const double* const pamp =
+      a.window_mode ? nullptr : push_amp_t<TRACE>(a.push, a.kick, wc, axis);
   const int kstep = pamp ? push_start(a.push, nullptr, a.kick_step, wc, a.n) : kNoPush;
   const unsigned pdur = push_dur(a.push);
 
@@ -894,7 +899,7 @@ __global__ void __launch_bounds__(64) zmpc_herdt_kernel(HerdtArgs a) {
     }
     // F_ext impulse on the state (:525-526), over the window's steps
     if ((unsigned)((int)i - kstep) < pdur)
-      xn[1] -= push_value(a.push, pamp, (unsigned)((int)i - kstep));
+      xn[1] -= push_value_t<TRACE>(a.push, pamp, (unsigned)((int)i - kstep));
     if (nxt != cur) cur = nxt;
     x[0] = xn[0];
     x[1] = xn[1];
@@ -936,12 +941,13 @@ __global__ void __launch_bounds__(64) zmpc_herdt_kernel(HerdtArgs a) {
 struct HerdtKernel {
   int MM;
   void (*fn)(HerdtArgs);
+  void (*fn_trace)(HerdtArgs);  // the instance that reads a per-walk trace
 };
-constexpr HerdtKernel kKernels[] = {{2, zmpc_herdt_kernel<2>},
-                                    {4, zmpc_herdt_kernel<4>},
-                                    {6, zmpc_herdt_kernel<6>},
-                                    {7, zmpc_herdt_kernel<7>},
-                                    {8, zmpc_herdt_kernel<8>}};
+constexpr HerdtKernel kKernels[] = {{2, zmpc_herdt_kernel<2>, zmpc_herdt_kernel<2, true>},
+                                    {4, zmpc_herdt_kernel<4>, zmpc_herdt_kernel<4, true>},
+                                    {6, zmpc_herdt_kernel<6>, zmpc_herdt_kernel<6, true>},
+                                    {7, zmpc_herdt_kernel<7>, zmpc_herdt_kernel<7, true>},
+                                    {8, zmpc_herdt_kernel<8>, zmpc_herdt_kernel<8, true>}};
 constexpr int kNumKernels = sizeof(kKernels) / sizeof(kKernels[0]);
 
 constexpr bool kernels_match_dispatch() {
@@ -995,7 +1001,8 @@ hipError_t launch(HerdtArgs a, const HerdtShape& shape, hipStream_t s) {
   hipError_t e = hipErrorInvalidValue;  // (no instance: the caller refuses such a count first)
   for (const HerdtKernel& k : kKernels) {
     if (k.MM != shape.MM) continue;
-    hipLaunchKernelGGL(k.fn, dim3((unsigned)blocks), dim3(64), shape.lds, s, a);
+    hipLaunchKernelGGL(a.push.tstride ? k.fn_trace : k.fn, dim3((unsigned)blocks), dim3(64),
+                       shape.lds, s, a);
     e = hipGetLastError();
   }
   const hipError_t ef = hipFreeAsync(a.ws, s);
@@ -1066,8 +1073,9 @@ hipError_t zmpc_launch_herdt_step(const zmpc_plan* p, const zmpc_herdt_params* p
 hipError_t zmpc_herdt_set_attrs() {
   hipError_t e = hipSuccess;
   for (const HerdtKernel& k : kKernels)
-    if (e == hipSuccess)
-      e = hipFuncSetAttribute((const void*)k.fn, hipFuncAttributeMaxDynamicSharedMemorySize,
-                              (int)kLdsCap);
+    for (auto fn : {k.fn, k.fn_trace})
+      if (e == hipSuccess)
+        e = hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                (int)kLdsCap);
   return e;
 }

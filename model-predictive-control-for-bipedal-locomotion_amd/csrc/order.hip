@@ -18,7 +18,8 @@ namespace {
 
 // Sort key: kick step (−1: none) in the high word, the kick as an order-preserving 32-bit image
 // of its float value in the low word (a scheduling key, so float precision is plenty).  A push
-// window (push.amp set) sorts by its start step and the larger |amp| of its axes.
+// window (push.amp set) sorts by its start step and the larger |amp| of its axes (of a trace: the
+// larger |dv[b, 0, ·]|).
 __global__ void __launch_bounds__(256) zmpc_kick_key_kernel(const double* __restrict__ kick,
                                                             const int64_t* __restrict__ ksteps,
                                                             int64_t kstep, PushArgs push, int64_t B,
@@ -31,8 +32,8 @@ __global__ void __launch_bounds__(256) zmpc_kick_key_kernel(const double* __rest
   const unsigned hi = (unsigned)(ks < 0 ? 0 : (ks >= 0x7fffffff ? 0x7fffffff : ks + 1));
   float kf;
   if (push.amp) {
-    kf = fabsf((float)push.amp[b * push.cols]);
-    if (push.cols == 2) kf = fmaxf(kf, fabsf((float)push.amp[b * 2 + 1]));
+    kf = fabsf((float)push.amp[b * push.astride]);
+    if (push.cols == 2) kf = fmaxf(kf, fabsf((float)push.amp[b * push.astride + 1]));
   } else {
     kf = (float)kick[b];
   }

@@ -81,26 +81,41 @@ __host__ __device__ constexpr int kffa_rows(int N) { return (N + 2) / 2 + 8; }
 // The push window of a pushed rollout (include/zmpc.h, "The push, stated once") as the strict and
 // Herdt kernels take it, by value inside their argument structs.  All zero means the legacy
 // one-sample y kick of the struct's own kick fields, so a zero-initialised argument struct filled
-// by name behaves as before.
+// by name behaves as before.  A per-walk trace (include/zmpc.h, "The trace, stated once") is the
+// same window with a value per (walk, step, axis): amp is dv [B, L, cols], tstride = cols and
+// astride = L·cols; a window has tstride = 0 and astride = cols.
 struct PushArgs {
-  const double* amp;     // [B, cols] device, or null: the legacy kick
+  const double* amp;     // [B, cols] device, or null: the legacy kick; a trace: dv [B, L, cols]
   const double* w;       // [dur] device profile, or null: ones (no product)
   const int64_t* steps;  // [B] start steps, or null: step
   int64_t step;
   int dur;     // D, clamped to n by the launcher (a push past the walk's end is truncated anyway)
   int cols;    // C, the columns of amp
   int col[2];  // the column of axis a (0: x, 1: y) in amp, −1: the axis is not pushed
+  int tstride;      // doubles between consecutive samples of a walk's trace, 0: a window
+  int64_t astride;  // doubles between consecutive walks of amp
 };
 
 // "no push" as a start step: (unsigned)(i − kNoPush) >= 2^31 for every timestep 0 <= i < 2^24
 constexpr int kNoPush = 0x7fffffff;
 
 // Where the amplitude of (walk b, axis) is read, null when the axis takes no push: amp[b, col] of
-// a push window, kick[b] on the y axis otherwise.
+// a push window (dv[b, 0, col] of a trace), kick[b] on the y axis otherwise.  TRACE fixes the form
+// at compile time for a kernel that keeps the trace in instantiations of its own (herdt.hip):
+// false strides by the window's columns, as before the trace existed.
+template <bool TRACE>
+__host__ __device__ inline const double* push_amp_t(const PushArgs& p, const double* kick,
+                                                    int64_t b, int axis) {
+  if (p.amp)
+    return p.col[axis] >= 0 ? p.amp + b * (TRACE ? p.astride : (int64_t)p.cols) + p.col[axis]
+                            : nullptr;
+  return (kick && axis == 1) ? kick + b : nullptr;
+}
+
+// ... with the form read from the struct: astride is the window's columns too
 __host__ __device__ inline const double* push_amp(const PushArgs& p, const double* kick,
                                                   int64_t b, int axis) {
-  if (p.amp) return p.col[axis] >= 0 ? p.amp + b * p.cols + p.col[axis] : nullptr;
-  return (kick && axis == 1) ? kick + b : nullptr;
+  return push_amp_t<true>(p, kick, b, axis);
 }
 
 // The start step of walk b's push in a walk of n samples, kNoPush outside [0, n − 1).
@@ -116,11 +131,18 @@ __host__ __device__ inline unsigned push_dur(const PushArgs& p) {
   return p.amp ? (unsigned)p.dur : 1u;
 }
 
-// What sample i + 1's velocity is lowered by at j = i − start, read at the point of use: the
-// amplitude itself without a profile, so that D = 1 is the legacy kick's arithmetic.
-__host__ __device__ inline double push_value(const PushArgs& p, const double* ap, unsigned j) {
+// What sample i + 1's velocity is lowered by at j = i − start, read at the point of use: a trace's
+// own entry of step j as it is; of a window the amplitude itself without a profile, so that D = 1
+// is the legacy kick's arithmetic.
+template <bool TRACE>
+__host__ __device__ inline double push_value_t(const PushArgs& p, const double* ap, unsigned j) {
+  if (TRACE) return ap[(size_t)j * (unsigned)p.tstride];
   const double am = *ap;
   return p.w ? am * p.w[j] : am;
+}
+
+__host__ __device__ inline double push_value(const PushArgs& p, const double* ap, unsigned j) {
+  return p.tstride ? push_value_t<true>(p, ap, j) : push_value_t<false>(p, ap, j);
 }
 
 // The arguments of one zmpc_rollout / zmpc_rollout_kicks / zmpc_rollout_pushed call
@@ -238,6 +260,12 @@ hipError_t zmpc_push_map_set_attrs();
 // (pushmap.hip): hist[b, s_b + d, a, :] −= amp[b, a]·Σ_j w_j·Ā^(d−j−1)·e1 on the axes of c.push.
 // hipErrorOutOfMemory: the stream-ordered workspace (4n doubles, 8n with a profile or D > 1)
 hipError_t zmpc_launch_push_response(const zmpc_plan* p, const RolloutCall& c, hipStream_t s);
+
+// the state response of a per-walk trace (c.push in trace form: tstride != 0) subtracted from an
+// unpushed history of a non-strict plan (trace.hip): one wave per walk, an O(n) scan, no workspace;
+// L: the samples of a walk's trace as the caller gave them (c.push.dur is clamped to n)
+hipError_t zmpc_launch_trace_response(const zmpc_plan* p, const RolloutCall& c, int64_t L,
+                                      hipStream_t s);
 
 // unconstrained rollout / step (rollout.hip)
 hipError_t zmpc_launch_rollout_unc(const zmpc_plan* p, const RolloutCall& c, hipStream_t s,

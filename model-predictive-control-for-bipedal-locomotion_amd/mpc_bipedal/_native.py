@@ -103,6 +103,9 @@ SIGNATURES = {
     "zmpc_rollout_kicks": (_C, [_P, _L, _L, _P, _P, _L, _P, _P, _P, _P, _P, _P]),
     # ... x0, push (const zmpc_push*, a ZmpcPush passed byref), hist, status, stream
     "zmpc_rollout_pushed": (_C, [_P, _L, _L, _P, _P, _L, _P, _P, _P, _P, _P]),
+    # ... x0, trace (const zmpc_trace*, a ZmpcTrace passed byref: it carries the stream), hist,
+    # status
+    "zmpc_rollout_traced": (_C, [_P, _L, _L, _P, _P, _L, _P, _P, _P, _P]),
     "zmpc_walk_metrics": (_C, [_P, _L, _L, _P, _P, _P, _L, _P, _P, _P]),
     "zmpc_rollout_metrics": (_C, [_P, _L, _L, _P, _P, _L, _P, _P, _L, _P, _P, _P, _P, _P]),
     "zmpc_push_map": (_C, [_P, _L, _L, _P, _P, _P, _L, _P, _P, _D, _D, _P, _P, _P, _P]),
@@ -116,6 +119,9 @@ SIGNATURES = {
     # ... x0, push (const zmpc_push*), hist, foot, status, stream
     "zmpc_herdt_rollout_pushed": (_C, [_P, _P, _L, _L, _P, _L, _P, _L, _P, _L, _P, _P, _P, _P,
                                        _P, _P]),
+    # ... x0, trace (const zmpc_trace*), hist, foot, status
+    "zmpc_herdt_rollout_traced": (_C, [_P, _P, _L, _L, _P, _L, _P, _L, _P, _L, _P, _P, _P, _P,
+                                       _P]),
     # plan, B, n, states, s_stride, lengths, states_out, nb_next, max_steps, max_footsteps (host);
     # no stream: synchronous, called as zmpc_plan_export is
     "zmpc_herdt_prepare": (_C, [_P, _L, _L, _P, _L, _P, _P, _P, _P, ctypes.POINTER(_I)]),
@@ -132,6 +138,14 @@ class ZmpcPush(ctypes.Structure):
     _fields_ = [("amp", ctypes.c_void_p), ("axes", ctypes.c_int32), ("steps", ctypes.c_void_p),
                 ("step", ctypes.c_int64), ("profile", ctypes.c_void_p),
                 ("duration", ctypes.c_int64)]
+
+
+class ZmpcTrace(ctypes.Structure):
+    """include/zmpc.h zmpc_trace: the per-walk disturbance trace of zmpc_rollout_traced and
+    zmpc_herdt_rollout_traced (device pointers as integers).  The calls take their stream here."""
+    _fields_ = [("dv", ctypes.c_void_p), ("axes", ctypes.c_int32), ("steps", ctypes.c_void_p),
+                ("step", ctypes.c_int64), ("length", ctypes.c_int64),
+                ("stream", ctypes.c_void_p)]
 
 
 _lib = None
@@ -177,6 +191,17 @@ def check(rc: int, what: str):
         if rc == ZMPC_ENOMEM:
             raise DeviceOutOfMemory(f"{what} failed ({rc}): {msg}")
         raise NativeError(f"{what} failed ({rc}): {msg}")
+
+
+def call_traced(name, device, trace, *args, raises=True):
+    """One launch of a symbol that takes its stream in a ZmpcTrace among its arguments: enter
+    HIP device `device`, put torch's current stream there into `trace` and call name(*args)."""
+    with torch.cuda.device(device):
+        trace.stream = torch.cuda.current_stream(device).cuda_stream
+        rc = getattr(load(), name)(*args)
+    if raises:
+        check(rc, name)
+    return rc
 
 
 def call(name, device, *args, after=(), raises=True):

@@ -22,7 +22,9 @@ A push that lasts several samples, with or without a force profile, has the resp
 
 ``Push`` describes the shove itself — force, direction, start step, duration, profile — for the
 pushed rollouts of every controller (``zmpc_rollout_pushed``, ``zmpc_herdt_rollout_pushed``;
-``Plan.rollout(push=)``, the batch methods of ``ZMPController``).
+``Plan.rollout(push=)``, the batch methods of ``ZMPController``).  ``PushTrace`` is the general
+disturbance: a force per walk, sample and axis (``zmpc_rollout_traced``,
+``zmpc_herdt_rollout_traced``; ``Plan.rollout(trace=)``).
 
 A Herdt walk has no fixed CoP bounds: ``zmpc_herdt_walk_metrics`` (``csrc/herdt_metrics.hip``)
 rebuilds the support box from the feet the QP chose and adds the divergent component of motion
@@ -564,6 +566,120 @@ class Push:
                     dvel[b, s + j, a] = amp[b, c] if self.profile is None \
                         else amp[b, c] * self.profile[j]
         return dvel
+
+
+class PushTrace:
+    """A disturbance trace per walk for a rollout (include/zmpc.h zmpc_trace, "The trace, stated
+    once"): walk b takes force[b, j] newtons during history step step_b + j, so two walks can be
+    shoved for different lengths, with different shapes, more than once, or with noise of their own.
+
+    force  [B, L, 2] newtons on (x, y), or [B, L]: the y axis, the reference's convention
+           (zmp_controller.py:105-106).  NumPy, or a float64 tensor on the plan's device.  A
+           column that is exactly zero everywhere leaves its axis out, as Push does
+    step   an int, or [B] start steps (a step outside [0, n − 1): no disturbance for that walk)
+
+    +F on an axis lowers that axis' velocity.  ``axes`` is "x", "y" or "xy", ``length`` is L.
+    ``from_velocity_steps`` takes the velocity steps dv = dt·F/m themselves; a device tensor is
+    then used as it is, without a copy.  ``scaled(k)`` is the trace with every entry times k."""
+
+    __slots__ = ("values", "unit", "step", "axes", "length")
+
+    def __init__(self, force, step=0):
+        v = _trace_values(force, "force")
+        if v.ndim == 2:
+            axes = "y"
+            v = v.reshape(v.shape[0], v.shape[1], 1)
+        elif v.ndim == 3 and v.shape[2] == 2:
+            zero = [bool((v[:, :, a] == 0).all()) for a in (0, 1)]
+            if zero[0]:
+                axes, v = "y", v[:, :, 1:2]  # (an all-zero trace is a y trace of zeros)
+            elif zero[1]:
+                axes, v = "x", v[:, :, 0:1]
+            else:
+                axes = "xy"
+        else:
+            raise ValueError(f"force must be [B, L, 2] or [B, L], got shape {tuple(v.shape)}")
+        self._set(v, "N", step, axes)
+
+    @classmethod
+    def from_velocity_steps(cls, dv, step=0, axes="xy"):
+        """The trace of the velocity steps dv [B, L, C] in m/s (C the columns of `axes`; [B, L]
+        with one axis), what the kernels read: dv[b, j, c] lowers the velocity of sample
+        step_b + j + 1."""
+        if axes not in AXES:
+            raise ValueError(f"axes must be 'x', 'y' or 'xy', got {axes!r}")
+        v = _trace_values(dv, "dv")
+        C = 2 if axes == "xy" else 1
+        if v.ndim == 2 and C == 1:
+            v = v.reshape(v.shape[0], v.shape[1], 1)
+        if v.ndim != 3 or v.shape[2] != C:
+            raise ValueError(f"dv must be [B, L, {C}] for axes {axes!r}"
+                             f"{' or [B, L]' if C == 1 else ''}, got shape {tuple(v.shape)}")
+        self = cls.__new__(cls)
+        self._set(v, "m/s", step, axes)
+        return self
+
+    def _set(self, v, unit, step, axes):
+        if v.shape[0] < 1 or v.shape[1] < 1:
+            raise ValueError(f"a trace needs B >= 1 walks and L >= 1 samples, got shape "
+                             f"{tuple(v.shape)}")
+        st = np.asarray(step)
+        if st.ndim > 1 or st.dtype.kind not in "iu":
+            raise ValueError("step must be an integer or a [B] integer array")
+        if st.ndim == 1 and st.shape[0] not in (1, v.shape[0]):
+            raise ValueError(f"step is for {st.shape[0]} walks, the trace holds {v.shape[0]}")
+        self.values, self.unit, self.axes, self.length = v, unit, axes, int(v.shape[1])
+        self.step = int(st) if st.ndim == 0 else st.astype(np.int64)
+
+    def __repr__(self):
+        return (f"PushTrace(axes={self.axes!r}, walks={self.batch()}, length={self.length}, "
+                f"step={self.step!r})")
+
+    def batch(self):
+        """The batch size the trace asks for: its B rows."""
+        return int(self.values.shape[0])
+
+    def scaled(self, k):
+        """The same trace with every entry times k (a new array; self is unchanged)."""
+        t = PushTrace.__new__(PushTrace)
+        t._set(self.values * float(k), self.unit, self.step, self.axes)
+        return t
+
+    def dv(self, dt, m, B):
+        """dv [B, L, C] = dt·F/m in m/s, C columns in the order of ``axes``: a NumPy array, or
+        the device tensor itself when the trace holds velocity steps on the device."""
+        if self.batch() != B:
+            raise ValueError(f"the trace is for {self.batch()} walks, the batch holds {B}")
+        if self.unit == "m/s":
+            return self.values
+        return dt * self.values / m
+
+    def velocity_steps(self, dt, m, B, n):
+        """dvel [B, n, 2]: what the velocity of sample i + 1 is lowered by at history step i, on
+        (x, y) — the statement of include/zmpc.h in NumPy, for the checkers."""
+        dv = self.dv(dt, m, B)
+        if not isinstance(dv, np.ndarray):
+            dv = dv.detach().cpu().numpy()
+        cols = [a for a in (0, 1) if AXES[self.axes] >> a & 1]
+        steps = np.broadcast_to(np.asarray(self.step, np.int64).reshape(-1), (B,))
+        dvel = np.zeros((B, n, 2))
+        for b in range(B):
+            s = int(steps[b])
+            if not 0 <= s < n - 1:
+                continue
+            k = min(self.length, n - 1 - s)
+            for c, a in enumerate(cols):
+                dvel[b, s:s + k, a] = dv[b, :k, c]
+        return dvel
+
+
+def _trace_values(a, name):
+    """A trace's entries: a float64 device tensor as it is, anything else as a float64 array."""
+    if hasattr(a, "data_ptr"):  # a torch tensor; analysis itself does not need torch
+        if str(a.dtype) != "torch.float64":
+            raise ValueError(f"a {name} tensor must be float64, got {a.dtype}")
+        return a
+    return np.asarray(a, np.float64)
 
 
 class PushMap:

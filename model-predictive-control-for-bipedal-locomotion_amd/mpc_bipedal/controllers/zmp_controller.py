@@ -18,7 +18,8 @@ the ZMP stay inside the support box, per walk, reduced on the device), ``critica
 unconstrained controller ``push_map`` / ``critical_force_exact`` (that push in closed form, at
 every step and in both directions, from one unpushed rollout).  The batch methods and
 ``critical_force`` also take a shove of any length, shape and planar direction
-(``push=analysis.Push(...)``; ``duration=``, ``profile=``) on every controller.  For the
+(``push=analysis.Push(...)``; ``duration=``, ``profile=``) on every controller, or a force trace
+per walk, sample and axis (``trace=analysis.PushTrace(...)``).  For the
 footstep-adapting controller the same two questions are ``herdt_walk_metrics`` (the support box
 rebuilt from the feet the QP chose, and the divergent component of motion as the verdict) and
 ``critical_force_herdt``.
@@ -30,8 +31,8 @@ from typing import Optional, Tuple
 import numpy as np
 import torch
 
-from ..analysis import (NHERDT_METRICS, NMETRICS, HerdtWalkMetrics, Push, PushMap, WalkMetrics,
-                        check_profile, planar_push, unit_directions)
+from ..analysis import (NHERDT_METRICS, NMETRICS, HerdtWalkMetrics, Push, PushMap, PushTrace,
+                        WalkMetrics, check_profile, planar_push, unit_directions)
 from ..config import MPCConfig
 from ..models.lipm_model import lipm_matrices
 from ..solver import get_plan
@@ -259,7 +260,7 @@ class ZMPController:
 
     def generate_com_trajectory_herdt_batch(self, x_init, v_ref, state_ref, F_ext=None,
                                             return_status: bool = False, push: Push = None,
-                                            walk_lengths=None):
+                                            walk_lengths=None, trace: PushTrace = None):
         """Many Herdt walks at once (addition): x_init [B,2,3] or None; v_ref [B,n,2] or a
         shared [n,2]; state_ref [B,n] or a shared [n] (State enums or int8 codes, NumPy or a
         device tensor, which stays on the device); F_ext [B] or None.  Returns (com [B,n,2],
@@ -275,9 +276,13 @@ class ZMPController:
                 [0, n_b) alone — its states and v_ref rows at or past n_b are replaced by row
                 n_b − 1, which is what the walk alone sees through the rollout's last-row
                 padding, and F_ext hits step n_b // 2 of each walk.  Output rows at or past n_b
-                are unspecified but finite."""
+                are unspecified but finite.
+        trace : an analysis.PushTrace — a disturbance per walk, sample and axis instead of F_ext or
+                push (zmpc_herdt_rollout_traced; together with either it raises ValueError)."""
         if push is not None and F_ext is not None:
             raise ValueError("give either F_ext or push, not both")
+        if trace is not None and (push is not None or F_ext is not None):
+            raise ValueError("give either trace or F_ext or push, not both")
         v = torch.as_tensor(v_ref, dtype=torch.float64)
         n = int(v.shape[-2])
         st = self._herdt_codes(state_ref)
@@ -291,6 +296,8 @@ class ZMPController:
             B = int(np.shape(walk_lengths)[0])
         elif push is not None:
             B = push.batch() or 1
+        elif trace is not None:
+            B = trace.batch()
         else:
             B = 1 if F_ext is None else int(np.size(F_ext))
         x0 = np.zeros((B, 2, 3)) if x_init is None else x_init
@@ -303,7 +310,8 @@ class ZMPController:
             push = Push(np.asarray(F_ext, np.float64).reshape(B), +1, steps)
         hist, foot, status = self._herdt_rollout(x0, v_ref, st, kick, n // 2,
                                                  check=not return_status, push=push,
-                                                 on_device=True, lengths=walk_lengths)
+                                                 on_device=True, lengths=walk_lengths,
+                                                 trace=trace)
         if return_status:
             return hist[..., 0], hist, foot, status
         return hist[..., 0], hist, foot
@@ -352,7 +360,7 @@ class ZMPController:
         return prm, (nb[0] if st.ndim == 1 else nb)
 
     def _herdt_rollout(self, x0, v_ref, st, kick, kick_step, check=True, push=None,
-                       on_device=False, lengths=None):
+                       on_device=False, lengths=None, trace=None):
         plan = self._plan()
         if on_device:
             prm, st, nb, v_ref = self._herdt_device(plan, st, v_ref, lengths)
@@ -360,7 +368,7 @@ class ZMPController:
             prm, nb = self._herdt_host(plan, st)
         hist, foot, status = plan.herdt_rollout(prm, v_ref, st, nb, x0, kick=kick,
                                                 kick_step=kick_step, push=push,
-                                                mass=self.config.m)
+                                                mass=self.config.m, trace=trace)
         if check:
             self._herdt_status(status)
         return hist, foot, status
@@ -368,7 +376,7 @@ class ZMPController:
     # ------------------------------------------------------------------ batched additions
     def generate_state_trajectory_batch(self, x_init, z_max, z_min, F_ext=None,
                                         force_step: Optional[int] = None, walk_lengths=None,
-                                        push: Push = None):
+                                        push: Push = None, trace: PushTrace = None):
         """Many walks at once; every input may be NumPy or a torch tensor.
 
         x_init : [B,2,3] initial (x-axis, y-axis) states, or None for zeros
@@ -383,10 +391,18 @@ class ZMPController:
                 (zmpc_rollout_pushed).  It carries its own start step(s): together with F_ext,
                 force_step or walk_lengths it raises ValueError (hist[b, :n_b] of a ragged walk
                 is still walk b's history; give the steps n_b // 2 in the push)
+        trace : an analysis.PushTrace — a disturbance per walk, sample and axis instead of F_ext
+                or push (zmpc_rollout_traced).  It carries its own start step(s) too: together with
+                F_ext, push, force_step or walk_lengths it raises ValueError
         Returns (hist [B,n,2,3], status [B]) on the plan's device.
         """
         if push is not None and F_ext is not None:
             raise ValueError("give either F_ext or push, not both")
+        if trace is not None and (push is not None or F_ext is not None):
+            raise ValueError("give either trace or F_ext or push, not both")
+        if trace is not None and (force_step is not None or walk_lengths is not None):
+            raise ValueError("a trace carries its own start step(s): force_step and walk_lengths "
+                             "belong to F_ext")
         if push is not None and (force_step is not None or walk_lengths is not None):
             raise ValueError("a push carries its own start step(s): force_step and walk_lengths "
                              "belong to F_ext")
@@ -396,6 +412,10 @@ class ZMPController:
             if x_init is None and zmax_t.dim() == 2 and push.batch():
                 x0 = x0.expand(push.batch(), 2, 3).contiguous()
             hist, st = plan.rollout(zmax_t, zmin_t, x0, push=push, mass=self.config.m)
+        elif trace is not None:
+            if x_init is None and zmax_t.dim() == 2:
+                x0 = x0.expand(trace.batch(), 2, 3).contiguous()
+            hist, st = plan.rollout(zmax_t, zmin_t, x0, trace=trace, mass=self.config.m)
         else:
             hist, st = plan.rollout(zmax_t, zmin_t, x0, kick=kick, kick_step=step)
         if plan.strict:
@@ -463,11 +483,11 @@ class ZMPController:
 
     def generate_com_trajectory_batch(self, x_init, z_max, z_min, F_ext=None,
                                       force_step: Optional[int] = None, walk_lengths=None,
-                                      push: Push = None):
+                                      push: Push = None, trace: PushTrace = None):
         """Batched generate_com_trajectory_wieber: (com [B,n,2], hist [B,n,2,3]) on device;
-        push as generate_state_trajectory_batch."""
+        push and trace as generate_state_trajectory_batch."""
         hist, _ = self.generate_state_trajectory_batch(x_init, z_max, z_min, F_ext, force_step,
-                                                       walk_lengths, push=push)
+                                                       walk_lengths, push=push, trace=trace)
         return hist[..., 0], hist
 
     def zmp(self, hist):
@@ -496,7 +516,8 @@ class ZMPController:
                        F_hi: float = 1000.0, iters: int = 30, max_violation: float = 1e-9,
                        max_com_dev: Optional[float] = None,
                        max_dcm_end: Optional[float] = None, walk_lengths=None,
-                       fused: bool = False, duration: int = 1, profile=None):
+                       fused: bool = False, duration: int = 1, profile=None,
+                       trace: PushTrace = None):
         """Largest push each scenario survives (addition): the question the F_ext sweep of
         run_compare_resistance.py:87-169 puts to the eye, answered by bisection on the device.
 
@@ -531,9 +552,27 @@ class ZMPController:
         critical_force_exact): F is then the magnitude of a push along that direction.  A scalar
         or [B] sign with duration 1 and no profile keeps the launches above; otherwise each
         evaluation is one pushed rollout (zmpc_rollout_pushed — on a strict plan the push window
-        of the strict kernels) plus walk_metrics, and fused=True raises ValueError."""
+        of the strict kernels) plus walk_metrics, and fused=True raises ValueError.
+
+        trace: an analysis.PushTrace instead of force_step, direction, duration and profile (given
+        together they raise ValueError).  The bisection then runs on the scale λ of each walk's
+        own trace, dv = λ·dv₁ with λ in [0, F_hi]: the returned bracket holds the largest multiple
+        of its trace that walk survives.  Everything else is as for a shove — one traced rollout
+        (zmpc_rollout_traced) plus walk_metrics per evaluation, the [B, L, C] velocity steps
+        scaled on the device — and fused=True raises ValueError."""
         D, w = check_profile(duration, profile)
         planar = np.ndim(direction) == 2
+        traced = trace is not None
+        if traced:
+            if not isinstance(trace, PushTrace):
+                raise ValueError(f"trace must be an analysis.PushTrace, got {type(trace).__name__}")
+            if force_step is not None or planar or D != 1 or w is not None or \
+                    not (np.ndim(direction) == 0 and direction == +1):
+                raise ValueError("a trace carries its own start steps, directions and shape: "
+                                 "force_step, direction, duration and profile belong to a push")
+            if fused:
+                raise ValueError("fused=True has no traced form: a trace runs a traced rollout "
+                                 "plus walk_metrics")
         shove = planar or D != 1 or w is not None
         if shove and fused:
             raise ValueError("fused=True has no pushed form: a shove (duration, profile or a "
@@ -544,7 +583,8 @@ class ZMPController:
         f64 = dict(dtype=torch.float64, device=dev)
         zmax_t, zmin_t, x0, B, n, lengths = self._scenario(
             plan, z_max, z_min, x_init, walk_lengths,
-            sized=(force_step, walk_lengths, _direction_size(direction, unit)), planar=True)
+            sized=(force_step, walk_lengths, _direction_size(direction, unit),
+                   np.empty(trace.batch()) if traced else None), planar=True)
         if not (F_hi > 0) or iters < 0:
             raise ValueError("need F_hi > 0 and iters >= 0")
         if planar:
@@ -556,7 +596,12 @@ class ZMPController:
             step = torch.as_tensor(step, dtype=torch.int64, device=dev)
         kick = torch.zeros(B, **f64)
         metrics = torch.empty((B, NMETRICS), **f64)
-        if shove:
+        if traced:
+            # (a copy of the trace at scale 1: the launch's buffer is rewritten per evaluation)
+            launch = plan.rollout_launcher(zmax_t, zmin_t, x0, trace=trace.scaled(1.0),
+                                           mass=self.config.m)
+            dv1 = launch.trace_dv.clone()  # [B, L, C] at λ = 1
+        elif shove:
             F1, d1 = _unit_push(None if planar else sign.cpu().numpy(), unit, B)
             st = step.cpu().numpy() if isinstance(step, torch.Tensor) else step
             push = Push(F1, d1, st, duration=D, profile=w)
@@ -571,7 +616,9 @@ class ZMPController:
         dt, mass = self.config.dt, self.config.m
 
         def passes(F):
-            if shove:
+            if traced:
+                launch.trace_dv.copy_(dv1 * F[:, None, None])
+            elif shove:
                 launch.push_amp.copy_(amp1 * F[:, None])
             else:
                 kick.copy_(dt * (sign * F) / mass)  # zmp_controller.py:106
@@ -613,7 +660,8 @@ class ZMPController:
     def critical_force_herdt(self, v_ref, state_ref, max_dcm_dev, x_init=None, force_step=None,
                              direction=+1, F_hi: float = 1000.0, iters: int = 30,
                              max_violation: float = 1e-9, max_com_dev: Optional[float] = None,
-                             duration: int = 1, profile=None, walk_lengths=None):
+                             duration: int = 1, profile=None, walk_lengths=None,
+                             trace: PushTrace = None):
         """Largest shove each scenario of the footstep-adapting controller survives (addition):
         critical_force for Herdt walks, with its bisection, bracket and NaN conventions.
 
@@ -648,8 +696,20 @@ class ZMPController:
         F_hi/2**iters; NaN in both where the walk fails unpushed; F_lo = F_hi = the search limit
         where it passes even there.  Bisection assumes that pass/fail is monotone in F.  That is
         an assumption here, as for strict plans in critical_force: the controller is piecewise
-        linear; on the walks of the tests the passing set was one interval."""
+        linear; on the walks of the tests the passing set was one interval.
+
+        trace: an analysis.PushTrace instead of force_step, direction, duration and profile (given
+        together they raise ValueError): the bisection runs on the scale λ in [0, F_hi] of each
+        walk's own trace, one zmpc_herdt_rollout_traced per evaluation."""
         D, w = check_profile(duration, profile)
+        traced = trace is not None
+        if traced:
+            if not isinstance(trace, PushTrace):
+                raise ValueError(f"trace must be an analysis.PushTrace, got {type(trace).__name__}")
+            if force_step is not None or np.ndim(direction) != 0 or direction != +1 or D != 1 \
+                    or w is not None:
+                raise ValueError("a trace carries its own start steps, directions and shape: "
+                                 "force_step, direction, duration and profile belong to a push")
         if max_dcm_dev is None or not (float(max_dcm_dev) > 0):
             raise ValueError("max_dcm_dev must be a positive bound in metres: the ZMP of a Herdt "
                              "walk never tells whether the robot fell, the DCM does")
@@ -663,7 +723,8 @@ class ZMPController:
         v = torch.as_tensor(v_ref, **f64).contiguous()
         n = int(v.shape[-2])
         st = self._herdt_codes(state_ref)
-        sized = (force_step, _direction_size(direction, unit), walk_lengths)
+        sized = (force_step, _direction_size(direction, unit), walk_lengths,
+                 np.empty(trace.batch()) if traced else None)
         sizes = [int(np.shape(a)[0]) for a in sized if a is not None and np.ndim(a) == 1]
         if x_init is not None:
             B = int(np.shape(x_init)[0])
@@ -685,10 +746,16 @@ class ZMPController:
             step = np.asarray(torch.as_tensor(step).cpu(), np.int64)
         F1, d1 = _unit_push(direction, unit, B)
         prm, st, nb, v = self._herdt_device(plan, st, v, walk_lengths)
-        launch = plan.herdt_rollout_launcher(prm, v, st, nb, x0,
-                                             Push(F1, d1, step, duration=D, profile=w),
-                                             self.config.m)
-        amp1 = launch.push_amp.clone()  # [B, C] for 1 N
+        if traced:
+            # (a copy of the trace at scale 1: the launch's buffer is rewritten per evaluation)
+            launch = plan.herdt_rollout_launcher(prm, v, st, nb, x0, mass=self.config.m,
+                                                 trace=trace.scaled(1.0))
+            scaled, amp1 = launch.trace_dv, launch.trace_dv.clone()  # [B, L, C] at λ = 1
+        else:
+            launch = plan.herdt_rollout_launcher(prm, v, st, nb, x0,
+                                                 Push(F1, d1, step, duration=D, profile=w),
+                                                 self.config.m)
+            scaled, amp1 = launch.push_amp, launch.push_amp.clone()  # [B, C] for 1 N
         metrics = torch.empty((B, NHERDT_METRICS), **f64)
         foot_ref = torch.empty_like(launch.foot)
         measure, measure_ref = (plan.herdt_walk_metrics_launcher(
@@ -697,7 +764,7 @@ class ZMPController:
         m = HerdtWalkMetrics(metrics)
 
         def passes(F):
-            launch.push_amp.copy_(amp1 * F[:, None])
+            scaled.copy_(amp1 * F.reshape((-1,) + (1,) * (amp1.dim() - 1)))
             launch()
             measure()
             ok = (m.viol_max <= max_violation).all(dim=1)  # (+inf and NaN fail)

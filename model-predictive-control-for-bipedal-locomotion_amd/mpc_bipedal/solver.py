@@ -25,6 +25,15 @@ _PLAN_CACHE_LOCK = threading.Lock()
 PLAN_CACHE_MAX = max(1, int(os.environ.get("ZMPC_PLAN_CACHE", "8")))
 
 # what Plan._out raises for a state history and for a metrics tensor
+class _Traced:
+    """What a traced launch reads: the _native.ZmpcTrace (it carries the stream) and the device
+    tensors it points to, dv [B, L, C] and the start steps [B] or None."""
+    __slots__ = ("struct", "dv", "steps")
+
+    def __init__(self, struct, dv, steps):
+        self.struct, self.dv, self.steps = struct, dv, steps
+
+
 _HIST_MSG = "hist must be a contiguous float64 [B, n, 2, 3] tensor on the plan's device"
 _METRICS_MSG = (f"out must be a contiguous float64 [B, {_native.NMETRICS}] tensor on the plan's "
                 "device")
@@ -229,6 +238,33 @@ class Plan:
                              None if prof is None else prof.data_ptr(), push.duration)
         return c, (amp, steps, prof)
 
+    def _trace_struct(self, trace, mass, B, kick=None, push=None):
+        """An analysis.PushTrace as the C-ABI takes it: a _Traced (the _native.ZmpcTrace and the
+        device tensors it points to).  A trace in newtons needs the robot's mass; velocity
+        steps on the plan's device are used as they are, without a copy.  kick, push: the
+        caller's other disturbances, which a trace excludes."""
+        from .analysis import AXES, PushTrace
+        if kick is not None or push is not None:
+            raise ValueError("give either trace or a kick or push, not both")
+        if not isinstance(trace, PushTrace):
+            raise ValueError(f"trace must be an analysis.PushTrace, got {type(trace).__name__}")
+        if trace.unit != "m/s" and (mass is None or not (float(mass) > 0)
+                                    or not np.isfinite(float(mass))):
+            raise ValueError("a trace in newtons needs the robot's mass in kg (mass=), finite and "
+                             "positive")
+        dev = self._device
+        dv = trace.dv(self.dt, None if mass is None else float(mass), B)
+        dv = torch.as_tensor(dv, dtype=torch.float64, device=dev).contiguous()
+        if isinstance(trace.step, int):
+            step, steps = trace.step, None
+        else:
+            step = -1
+            steps = torch.as_tensor(np.broadcast_to(trace.step, (B,)).copy(), device=dev)
+        c = _native.ZmpcTrace(dv.data_ptr(), AXES[trace.axes],
+                              None if steps is None else steps.data_ptr(), step, trace.length,
+                              None)
+        return _Traced(c, dv, steps)
+
     # -- launches --------------------------------------------------------------------------
     def _launcher(self, name, args, **attrs):
         """A zero-argument callable that re-issues name(*args, current stream) and carries
@@ -240,6 +276,20 @@ class Plan:
         def launch():
             stream = torch.cuda.current_stream(dev).cuda_stream
             rc = fn(*args, ctypes.c_void_p(stream))
+            if rc != 0:
+                _native.check(rc, name)
+        launch.__dict__.update(attrs)
+        return launch
+
+    def _launcher_traced(self, name, args, c, **attrs):
+        """_launcher for the calls that take their stream in a ZmpcTrace `c` among args: one
+        launch is one stream lookup, one store into the struct and one ctypes call."""
+        fn = getattr(_native.load(), name)
+        dev = self.device
+
+        def launch():
+            c.stream = torch.cuda.current_stream(dev).cuda_stream
+            rc = fn(*args)
             if rc != 0:
                 _native.check(rc, name)
         launch.__dict__.update(attrs)
@@ -260,26 +310,37 @@ class Plan:
         return out, st
 
     def rollout_launcher(self, zmax, zmin, x0, kick=None, kick_step=-1, hist=None, status=None,
-                         push=None, mass=None):
+                         push=None, mass=None, trace=None):
         """Validate once and return a zero-argument callable that re-issues the same rollout
         launch on the current stream (one ctypes call, no tensor checks): for timing loops
         and graph capture.  The tensors must stay alive while the launcher is used.  push, mass:
         as rollout; launch.push_amp is then the [B, C] amplitude tensor the launch reads (write
-        new amplitudes into it between launches, as critical_force does)."""
+        new amplitudes into it between launches, as critical_force does).  trace: an
+        analysis.PushTrace instead; launch.trace_dv is then the [B, L, C] tensor of velocity steps
+        the launch reads."""
         hist, status, (name, args, keep) = self._rollout_args(zmax, zmin, x0, kick, kick_step,
-                                                              hist, status, push, mass)
+                                                              hist, status, push, mass, trace)
+        if trace is not None:
+            traced = keep[-1]
+            return self._launcher_traced(name, args, traced.struct, hist=hist, status=status,
+                                         inputs=keep, push_amp=None, trace_dv=traced.dv)
         return self._launcher(name, args, hist=hist, status=status, inputs=keep,
                               push_amp=keep[-1][0] if push is not None else None)
 
     def rollout(self, zmax, zmin, x0, kick=None, kick_step=-1, hist=None, status=None,
-                push=None, mass=None):
+                push=None, mass=None, trace=None):
         """Batched Wieber rollout → hist [B,n,2,3] (device), status [B] (see _rollout_args).
         push: an analysis.Push — a shove of any length, shape and direction instead of the
         one-sample y kick (zmpc_rollout_pushed; not together with kick); mass: the robot's mass
-        in kg, needed with push."""
-        hist, status, (name, args, _) = self._rollout_args(zmax, zmin, x0, kick, kick_step, hist,
-                                                           status, push, mass)
-        _native.call(name, self.device, *args)
+        in kg, needed with push.  trace: an analysis.PushTrace — a disturbance per walk, sample
+        and axis (zmpc_rollout_traced; not together with kick or push); mass is needed when the
+        trace is in newtons."""
+        hist, status, (name, args, keep) = self._rollout_args(zmax, zmin, x0, kick, kick_step,
+                                                              hist, status, push, mass, trace)
+        if trace is not None:
+            _native.call_traced(name, self.device, keep[-1].struct, *args)
+        else:
+            _native.call(name, self.device, *args)
         return hist, status
 
     def _walk_inputs(self, zmax, zmin, x0):
@@ -288,7 +349,8 @@ class Plan:
         zmax, zmin, bstride = self._bounds(zmax, zmin, B)
         return zmax, zmin, x0, B, int(zmax.shape[-2]), bstride
 
-    def _rollout_args(self, zmax, zmin, x0, kick, kick_step, hist, status, push=None, mass=None):
+    def _rollout_args(self, zmax, zmin, x0, kick, kick_step, hist, status, push=None, mass=None,
+                      trace=None):
         """Batched Wieber rollout → hist [B,n,2,3] (device), status [B].
 
         zmax/zmin: [B,n,2] per-walk CoP bounds, or [n,2] one CoP shared by every walk;
@@ -302,6 +364,13 @@ class Plan:
             status = torch.empty(B, dtype=torch.int32, device=self._device)
         walks = (self._live(), B, n, _ptr(zmax), _ptr(zmin), bstride, _ptr(x0))
         outs = (_ptr(hist), _ptr(status))
+        if trace is not None:
+            traced = self._trace_struct(trace, mass, B, kick, push)
+            # (the struct carries the stream: no stream argument follows; what the arguments
+            # point to ends with the _Traced, by which the callers name the struct and dv)
+            return hist, status, ("zmpc_rollout_traced",
+                                  walks + (ctypes.addressof(traced.struct),) + outs,
+                                  (zmax, zmin, x0, traced))
         if push is not None:
             c, keep = self._push_struct(push, mass, B, kick)
             # (the arguments hold the struct's address: it lives in what the launcher keeps)
@@ -437,7 +506,7 @@ class Plan:
 
     # -- Herdt joint footstep QP (zmpc_herdt_rollout / zmpc_herdt_step) --------------------
     def _herdt_rollout_args(self, params, v_ref, states, nb_next, x0, kick, kick_step, push, mass,
-                            hist=None, foot=None, status=None):
+                            hist=None, foot=None, status=None, trace=None):
         """The checked arguments of one Herdt rollout → (hist, foot, status, (symbol, its
         arguments without the stream, what they point to)); hist, foot, status: tensors to write
         into, or None for new ones."""
@@ -467,7 +536,11 @@ class Plan:
                          "foot must be a contiguous float64 [B, n, 2] tensor on the plan's device")
         status = self._out(status, (B,), torch.int32,
                            "status must be a contiguous int32 [B] tensor on the plan's device")
-        if push is not None:
+        if trace is not None:
+            keep = self._trace_struct(trace, mass, B, kick, push)  # (a _Traced, named below)
+            c = keep.struct
+            name, disturbance = "zmpc_herdt_rollout_traced", (ctypes.addressof(c),)
+        elif push is not None:
             c, keep = self._push_struct(push, mass, B, kick)
             # (the arguments hold the struct's address: it lives in what the caller keeps)
             name, disturbance = "zmpc_herdt_rollout_pushed", (ctypes.addressof(c),)
@@ -479,28 +552,39 @@ class Plan:
         return hist, foot, status, (name, args, (params, v, st, nb, x0, kick_t, c, keep))
 
     def herdt_rollout(self, params, v_ref, states, nb_next, x0, kick=None, kick_step=-1,
-                      push=None, mass=None):
+                      push=None, mass=None, trace=None):
         """Batched generate_com_trajectory_herdt → (hist [B,n,2,3], foot [B,n,2], status [B]).
 
         v_ref [B,n,2] or a shared [n,2]; states [B,n] or [n] int8 codes; nb_next [B,n] or [n]
         int32 (find_nb_steps of the padded states, first element); x0 [B,2,3]; kick [B] or
         None: y-velocity impulse at kick_step.  params: controllers.herdt.HerdtParams.
         push: an analysis.Push instead of the kick (zmpc_herdt_rollout_pushed), with mass in kg.
+        trace: an analysis.PushTrace instead of either (zmpc_herdt_rollout_traced).
         """
-        hist, foot, status, (name, args, _) = self._herdt_rollout_args(
-            params, v_ref, states, nb_next, x0, kick, kick_step, push, mass)
-        _native.call(name, self.device, *args)
+        hist, foot, status, (name, args, keep) = self._herdt_rollout_args(
+            params, v_ref, states, nb_next, x0, kick, kick_step, push, mass, trace=trace)
+        if trace is not None:
+            _native.call_traced(name, self.device, keep[-1].struct, *args)
+        else:
+            _native.call(name, self.device, *args)
         return hist, foot, status
 
-    def herdt_rollout_launcher(self, params, v_ref, states, nb_next, x0, push, mass, hist=None,
-                               foot=None, status=None):
+    def herdt_rollout_launcher(self, params, v_ref, states, nb_next, x0, push=None, mass=None,
+                               hist=None, foot=None, status=None, trace=None):
         """rollout_launcher's counterpart for pushed Herdt walks: validate once and return a
         zero-argument callable that re-issues zmpc_herdt_rollout_pushed on the current stream.
         launch.hist, launch.foot, launch.status are its outputs, launch.states the int8 states on
         the device and launch.push_amp the [B, C] amplitude tensor the launch reads (write new
-        amplitudes into it between launches, as critical_force_herdt does)."""
+        amplitudes into it between launches, as critical_force_herdt does).  trace: an
+        analysis.PushTrace instead of push (zmpc_herdt_rollout_traced); launch.trace_dv is then
+        the [B, L, C] tensor of velocity steps the launch reads."""
         hist, foot, status, (name, args, keep) = self._herdt_rollout_args(
-            params, v_ref, states, nb_next, x0, None, -1, push, mass, hist, foot, status)
+            params, v_ref, states, nb_next, x0, None, -1, push, mass, hist, foot, status, trace)
+        if trace is not None:
+            traced = keep[-1]
+            return self._launcher_traced(name, args, traced.struct, hist=hist, foot=foot,
+                                         status=status, inputs=keep, states=keep[2],
+                                         push_amp=None, trace_dv=traced.dv)
         return self._launcher(name, args, hist=hist, foot=foot, status=status, inputs=keep,
                               states=keep[2], push_amp=keep[-1][0])
 

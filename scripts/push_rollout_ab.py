@@ -209,10 +209,14 @@ def main():
     ap.add_argument("--compare-new", default=None)
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--launches", type=int, default=3)
+    ap.add_argument("--duration", type=int, default=D,
+                    help="samples of the push window of the *_push_xy forms (the record names "
+                         "them *_push_xy_d20 whatever the value)")
     ap.add_argument("--legacy-only", action="store_true",
                     help="time the *_kick forms alone (the same sequence of launches for both "
                          "builds: the A/B proper)")
     args = ap.parse_args()
+    globals()["D"] = args.duration
     os.makedirs(args.out, exist_ok=True)
     if args.compare_parent:
         return compare(args.compare_parent.split(","), args.compare_new.split(","), args.out)
@@ -236,6 +240,7 @@ def main():
             ms[k].append(timed(fn, args.launches))
     torch.cuda.synchronize()
     rec = {"library": os.path.basename(_native.LIB_PATH), "pushed_entry_points": pushed,
+           "push_duration": D,
            "rounds": args.rounds, "launches_per_round": args.launches, "ms_rounds": ms,
            "ms": {k: {"median": float(np.median(v)), "min": min(v), "max": max(v)}
                   for k, v in ms.items()}}
