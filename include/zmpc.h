@@ -584,6 +584,63 @@ int zmpc_herdt_rollout_traced(const zmpc_plan* plan, const zmpc_herdt_params* pa
                               double* hist, double* foot, int32_t* status);
 
 /*
+ * Trace margin: the exact critical scale of a trace, K draws per walk, from one unpushed history of
+ * an unconstrained plan.  The closed loop is linear and time-invariant, so under λ times a trace
+ * the ZMP of sample i is z0_i + λ·ρ_i, and the largest λ a walk survives is a minimum of quotients
+ * over its samples: the argument of zmpc_push_map with a response per row instead of one per batch.
+ * No rollout is run per evaluation and no history is written: K random draws of a disturbance per
+ * nominal walk cost one unpushed zmpc_rollout of the B walks and this one launch over B·K rows.
+ *
+ *   hist [B, n, 2, 3] : an unpushed history; read, never written
+ *   zmax, zmin, bounds_stride, lengths : as zmpc_walk_metrics and zmpc_push_map (n_b clamped to
+ *                       [1, n] the same way)
+ *   draws = K >= 1    : the trace describes R = B·K rows, row r belongs to walk b = r / K;
+ *                       trace->dv is [R, L, C], trace->steps [R] or NULL.  "The trace, stated once"
+ *                       holds per row: where the value acts, the sign, truncation at the walk's end
+ *                       (n_b), and entries that reach no sample are never read
+ *   scale [R, 2], limit [R, 2] int32 or NULL
+ *
+ * The trace margin, stated once.  Per row r with start step s and requested axis a,
+ *     δ_s = 0,   δ_(i+1) = Ā·δ_i + e1·dv[r, i − s, col(a)]        (Ā = A − B·kxᵀ as zmpc_push_map)
+ *     ρ_i^a = −(δ_i^a[0] − (h/g)·δ_i^a[2])                         (uncontracted)
+ * z0 is the uncontracted ZMP of hist as in zmpc_walk_metrics, t = max_violation,
+ * up_i = (zmax_i − z0_i) + t and dn_i = (z0_i − zmin_i) + t.  Then
+ *     scale[r, 0] = min over s < i < n_b and the requested axes of
+ *                   up_i/ρ_i where ρ_i > 0,  dn_i/(−ρ_i) where ρ_i < 0,  +inf otherwise
+ * and scale[r, 1] is the same with up and dn swapped: the largest multiple of the negated trace.
+ * The quotient is an IEEE division; no candidate is formed from ρ = 0 and no 0·inf is formed, so a
+ * sample exactly on its bound with t = 0 gives 0.  limit[r, k] = 2·i + a of the smallest (i, a)
+ * that attains the minimum (a = 0 for x, 1 for y; i before a), −1 for +inf and NaN entries.
+ *   - A walk that fails the nominal test on either axis (zmpc_walk_metrics' test over all i < n_b,
+ *     the samples at or before s included; a non-finite state value in a live sample) gives NaN and
+ *     −1 in every row of that walk.
+ *   - A start step outside [0, n_b − 1), or an all-zero trace, gives +inf and −1 (unless the walk is
+ *     NaN by the rule above).
+ *   - A non-finite entry of dv gives unspecified values in its own row only and never causes an
+ *     out-of-range access.
+ *   - Two calls on the same input agree bit for bit; a row's result does not depend on the batch it
+ *     sits in; a call with K draws equals the K one-draw calls on the same walk bit for bit.
+ * One wavefront per row, the scan of zmpc_rollout_traced in its order of sums, the six propagators
+ * per launch from the plan's kx and step constants: O(n) per row, no workspace, no table, and no
+ * limit on n from LDS (n <= 2^30: limit holds 2·i + a).  It agrees with the extended-precision
+ * statement to 1e-11 relative, the bar of forms that compute the same solution.
+ *
+ * The call takes no `void* stream`: as for the two traced rollouts above the stream travels in
+ * trace->stream, so the stream-contract table (tests/stream_cases.py) does not reach it;
+ * tests/test_gpu_trace_margin.py holds it to the same contract.
+ * ZMPC_ESTATE before any device call: a strict plan (a clamped response is not affine in the
+ * scale; bisect with ZMPController.critical_force).  ZMPC_EINVAL before any device call: NULL plan
+ * or trace; with B > 0, NULL dv, hist, zmax, zmin or scale; B < 0 or n < 1; draws < 1; B·draws
+ * beyond the batch limit (2^31 − 1); axes outside 1..3; length < 1 or too large (as
+ * zmpc_rollout_traced, over B·draws rows); max_violation negative or NaN; a bad bounds_stride.
+ * B = 0 does nothing.  Nothing is launched on a refusal.  Additive to ABI 7.
+ */
+int zmpc_trace_margin(const zmpc_plan* plan, int64_t B, int64_t n, const double* hist,
+                      const double* zmax, const double* zmin, int64_t bounds_stride,
+                      const int64_t* lengths, int64_t draws, const zmpc_trace* trace,
+                      double max_violation, double* scale, int32_t* limit);
+
+/*
  * Per-walk survival metrics of a Herdt rollout, reduced on the device: did the footstep-adapting
  * controller stay up?  zmpc_walk_metrics needs fixed CoP bounds; a Herdt walk has none, its
  * support box follows the footsteps the QP chose.  Here the box is rebuilt from the rollout's own

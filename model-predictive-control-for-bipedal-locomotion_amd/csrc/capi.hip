@@ -632,6 +632,39 @@ int zmpc_push_map_shaped(const zmpc_plan* P, int64_t B, int64_t n, const double*
                        stream);
 }
 
+int zmpc_trace_margin(const zmpc_plan* P, int64_t B, int64_t n, const double* hist,
+                      const double* zmax, const double* zmin, int64_t bounds_stride,
+                      const int64_t* lengths, int64_t draws, const zmpc_trace* trace,
+                      double max_violation, double* scale, int32_t* limit) {
+  g_err.clear();
+  if (!P) return fail(ZMPC_EINVAL, "NULL plan");
+  if (B < 0 || n < 1) return fail(ZMPC_EINVAL, "need B >= 0 and n >= 1");
+  if (draws < 1) return fail(ZMPC_EINVAL, "need draws >= 1 (traces per walk)");
+  if (B > 0x7fffffff / draws) return fail(ZMPC_EINVAL, "batch too large (B * draws rows)");
+  const int rc = trace_check(trace, B * draws);
+  if (rc != ZMPC_OK) return rc;
+  if (!(max_violation >= 0)) return fail(ZMPC_EINVAL, "need max_violation >= 0");
+  if (bounds_stride != 0 && bounds_stride < 2 * n)
+    return fail(ZMPC_EINVAL, "bounds_stride must be 0 (shared CoP) or >= 2n");
+  if (B > 0 && (!hist || !zmax || !zmin || !scale))
+    return fail(ZMPC_EINVAL, "NULL array argument");
+  // (no LDS per sample, so none of the rollouts' 2^24; limit holds 2·i + a in an int32)
+  if (n > (1 << 30)) return fail(ZMPC_EINVAL, "walk too long (limit holds 2 * i + a in an int32)");
+  // refused before any device call, nothing is launched
+  if (P->strict)
+    return fail(ZMPC_ESTATE,
+                "zmpc_trace_margin: the ZMP response of a strict (clamped) controller is not "
+                "affine in the trace's scale (bisect over traced rollouts instead: "
+                "ZMPController.critical_force)");
+  if (B == 0) return ZMPC_OK;
+  DeviceGuard g(P->device);
+  if (g.err != hipSuccess) return hip_fail(g.err, "hipSetDevice");
+  const MarginCall c{B,     n,     hist,          zmax,          zmin,  bounds_stride, lengths,
+                     draws, trace_args(trace, n), trace->length, max_violation, scale, limit};
+  return launch_result(zmpc_launch_trace_margin(P, c, (hipStream_t)trace->stream), std::string(),
+                       "zmpc_trace_margin");
+}
+
 static int herdt_check(const zmpc_plan* P, const zmpc_herdt_params* prm, int64_t B) {
   if (!P || !prm) return fail(ZMPC_EINVAL, "NULL plan or params");
   if (B < 0) return fail(ZMPC_EINVAL, "B < 0");

@@ -23,42 +23,11 @@
 // Every sum runs in an order fixed by lane and block numbers alone, uncontracted: two calls agree
 // bit for bit, a walk gives the same bits alone and inside any batch, and an all-zero trace
 // subtracts +0 from every entry.  No index depends on a value of dv.
-#include "zmpc_internal.h"
+#include "trace_scan.h"
 
 namespace {
 
 #pragma clang fp contract(off)
-
-struct tpair_t {
-  double x, y;
-};
-
-struct TMat3 {
-  double a[9];
-};
-
-// Walks per workgroup (one wave each)
-constexpr int kTraceWaves = 4;
-
-__device__ __forceinline__ TMat3 tmul(const TMat3& p, const TMat3& q) {
-  TMat3 s;
-#pragma unroll
-  for (int i = 0; i < 3; ++i)
-#pragma unroll
-    for (int j = 0; j < 3; ++j)
-      s.a[3 * i + j] = p.a[3 * i] * q.a[j] + p.a[3 * i + 1] * q.a[3 + j] + p.a[3 * i + 2] * q.a[6 + j];
-  return s;
-}
-
-// v += m·t
-__device__ __forceinline__ void tmac(const TMat3& m, const double t[3], double v[3]) {
-  const double x = m.a[0] * t[0] + m.a[1] * t[1] + m.a[2] * t[2];
-  const double y = m.a[3] * t[0] + m.a[4] * t[1] + m.a[5] * t[2];
-  const double z = m.a[6] * t[0] + m.a[7] * t[1] + m.a[8] * t[2];
-  v[0] += x;
-  v[1] += y;
-  v[2] += z;
-}
 
 // cx, cy: the column of an axis in dv, −1 for an axis that is not requested; L: the samples of a
 // walk's trace, `cols` doubles each.
@@ -73,31 +42,9 @@ zmpc_trace_add_kernel(int64_t B, int64_t n, const double* __restrict__ kx, doubl
   const int64_t s = steps ? steps[b] : step;
   if (s < 0 || s >= n - 1) return;  // no disturbance for this walk (wave-uniform)
 
-  const double k0 = kx[0], k1 = kx[1], k2 = kx[2];
-  TMat3 P[6];  // Ā^(2^r)
-  P[0].a[0] = 1.0 - T3_6 * k0;
-  P[0].a[1] = T - T3_6 * k1;
-  P[0].a[2] = T2_2 - T3_6 * k2;
-  P[0].a[3] = 0.0 - T2_2 * k0;
-  P[0].a[4] = 1.0 - T2_2 * k1;
-  P[0].a[5] = T - T2_2 * k2;
-  P[0].a[6] = 0.0 - T * k0;
-  P[0].a[7] = 0.0 - T * k1;
-  P[0].a[8] = 1.0 - T * k2;
-#pragma unroll
-  for (int r = 1; r < 6; ++r) P[r] = tmul(P[r - 1], P[r - 1]);
-  // Q = Ā^(l+1): the powers of the set bits of l + 1, low bit first (bit 6: lane 63 alone)
-  TMat3 Q = P[0];
-  {
-    bool have = false;
-#pragma unroll
-    for (int r = 0; r < 6; ++r)
-      if (((lane + 1) >> r) & 1) {
-        Q = have ? tmul(P[r], Q) : P[r];
-        have = true;
-      }
-    if (lane == 63) Q = tmul(P[5], P[5]);
-  }
+  TMat3 P[6], Q;  // Ā^(2^r) and the lane's Ā^(l+1) (trace_scan.h)
+  trace_propagators(trace_closed_loop(kx, T, T2_2, T3_6), lane,
+                    [&](int r, const TMat3& m) { P[r] = m; }, Q);
 
   const int64_t first = s + 1;              // the first sample the trace moves
   const int64_t live = n - first;           // samples first .. n − 1, >= 1
@@ -123,23 +70,7 @@ zmpc_trace_add_kernel(int64_t B, int64_t n, const double* __restrict__ kx, doubl
       }
     }
     double v[2][3] = {{0.0, ux, 0.0}, {0.0, uy, 0.0}};
-#pragma unroll
-    for (int r = 0; r < 6; ++r) {
-      const int d = 1 << r;
-#pragma unroll
-      for (int a = 0; a < 2; ++a) {
-        double t[3];
-#pragma unroll
-        for (int c = 0; c < 3; ++c) t[c] = __shfl_up(v[a][c], d);
-        if (lane >= d) tmac(P[r], t, v[a]);
-      }
-    }
-#pragma unroll
-    for (int a = 0; a < 2; ++a) {
-      tmac(Q, carry[a], v[a]);
-#pragma unroll
-      for (int c = 0; c < 3; ++c) carry[a][c] = __shfl(v[a][c], 63);
-    }
+    trace_block_scan(P, Q, lane, carry, v);
     // the block's pairs 3·base + 64q + l, q = 0 .. 2: sample (64q + l) / 3 of the block, slot m
 #pragma unroll
     for (int q = 0; q < 3; ++q) {

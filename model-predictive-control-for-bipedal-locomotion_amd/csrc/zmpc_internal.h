@@ -267,6 +267,25 @@ hipError_t zmpc_launch_push_response(const zmpc_plan* p, const RolloutCall& c, h
 hipError_t zmpc_launch_trace_response(const zmpc_plan* p, const RolloutCall& c, int64_t L,
                                       hipStream_t s);
 
+// The arguments of one zmpc_trace_margin call: B walks with `draws` rows each; push is the trace
+// of the B·draws rows in trace form (trace_args), L its samples per row as the caller gave them.
+struct MarginCall {
+  int64_t B, n;
+  const double *hist, *zmax, *zmin;
+  int64_t bstride;
+  const int64_t* lengths;  // may be null
+  int64_t draws;
+  PushArgs push;
+  int64_t L;
+  double t;        // max_violation
+  double* scale;   // [B·draws, 2]
+  int32_t* limit;  // [B·draws, 2], may be null
+};
+
+// the exact critical scale of every row's trace from an unpushed history of a non-strict plan
+// (trace_margin.hip): one wave per row, trace.hip's scan, no workspace
+hipError_t zmpc_launch_trace_margin(const zmpc_plan* p, const MarginCall& c, hipStream_t s);
+
 // unconstrained rollout / step (rollout.hip)
 hipError_t zmpc_launch_rollout_unc(const zmpc_plan* p, const RolloutCall& c, hipStream_t s,
                                    std::string* why);

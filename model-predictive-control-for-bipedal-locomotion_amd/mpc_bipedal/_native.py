@@ -106,6 +106,9 @@ SIGNATURES = {
     # ... x0, trace (const zmpc_trace*, a ZmpcTrace passed byref: it carries the stream), hist,
     # status
     "zmpc_rollout_traced": (_C, [_P, _L, _L, _P, _P, _L, _P, _P, _P, _P]),
+    # plan, B, n, hist, zmax, zmin, bounds_stride, lengths, draws, trace (const zmpc_trace*: it
+    # carries the stream), max_violation, scale, limit
+    "zmpc_trace_margin": (_C, [_P, _L, _L, _P, _P, _P, _L, _P, _L, _P, _D, _P, _P]),
     "zmpc_walk_metrics": (_C, [_P, _L, _L, _P, _P, _P, _L, _P, _P, _P]),
     "zmpc_rollout_metrics": (_C, [_P, _L, _L, _P, _P, _L, _P, _P, _L, _P, _P, _P, _P, _P]),
     "zmpc_push_map": (_C, [_P, _L, _L, _P, _P, _P, _L, _P, _P, _D, _D, _P, _P, _P, _P]),
@@ -141,8 +144,9 @@ class ZmpcPush(ctypes.Structure):
 
 
 class ZmpcTrace(ctypes.Structure):
-    """include/zmpc.h zmpc_trace: the per-walk disturbance trace of zmpc_rollout_traced and
-    zmpc_herdt_rollout_traced (device pointers as integers).  The calls take their stream here."""
+    """include/zmpc.h zmpc_trace: the per-walk disturbance trace of zmpc_rollout_traced,
+    zmpc_herdt_rollout_traced and zmpc_trace_margin (device pointers as integers).  The calls take
+    their stream here."""
     _fields_ = [("dv", ctypes.c_void_p), ("axes", ctypes.c_int32), ("steps", ctypes.c_void_p),
                 ("step", ctypes.c_int64), ("length", ctypes.c_int64),
                 ("stream", ctypes.c_void_p)]

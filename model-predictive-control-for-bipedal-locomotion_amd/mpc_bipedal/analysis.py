@@ -774,6 +774,118 @@ class PushMap:
         return val, np.where(none, -1, idx // 2), np.where(none, 0, 1 - 2 * (idx % 2))
 
 
+def trace_margin_reference(hist, zmax, zmin, dv, steps, Abar, hg, draws=1, axes="xy", lengths=None,
+                           max_violation=0.0):
+    """The statement of include/zmpc.h zmpc_trace_margin in NumPy, with division: the checker of
+    the kernel, never a fallback → (scale [B, K, 2] float64, limit [B, K, 2] int32).
+
+    hist [B, n, 2, 3] unpushed; zmax, zmin [B, n, 2] or a shared [n, 2]; dv [B·K, L, C] velocity
+    steps in m/s, C the columns of `axes`; steps an int or [B·K] start steps; Abar [3, 3] the closed
+    loop A − B·kxᵀ; hg = h/g; lengths [B] live samples or None.  Row b·K + k is draw k of walk b."""
+    hist = np.asarray(hist, np.float64)
+    zmax, zmin = np.asarray(zmax, np.float64), np.asarray(zmin, np.float64)
+    dv = np.asarray(dv, np.float64)
+    dv = dv.reshape(dv.shape[0], dv.shape[1], -1)
+    Abar = np.asarray(Abar, np.float64).reshape(3, 3)
+    B, n = hist.shape[:2]
+    K, t = int(draws), float(max_violation)
+    cols = [a for a in (0, 1) if AXES[axes] >> a & 1]
+    if dv.shape[0] != B * K or dv.shape[2] != len(cols):
+        raise ValueError(f"dv must be [B·K, L, {len(cols)}] = [{B * K}, L, {len(cols)}], got "
+                         f"{dv.shape}")
+    steps = np.broadcast_to(np.asarray(steps, np.int64).reshape(-1), (B * K,))
+    scale = np.full((B, K, 2), np.inf)
+    limit = np.full((B, K, 2), -1, np.int32)
+    for b in range(B):
+        nb = n if lengths is None else min(max(int(lengths[b]), 1), n)
+        hi = (zmax if zmax.ndim == 2 else zmax[b])[:nb]
+        lo = (zmin if zmin.ndim == 2 else zmin[b])[:nb]
+        st = hist[b, :nb]
+        z = st[:, :, 0] - hg * st[:, :, 2]                               # [nb, 2]
+        v = np.fmax(np.fmax(z - hi, lo - z), 0.0)
+        if not np.isfinite(st).all() or (v > t).any():
+            scale[b] = np.nan
+            continue
+        up, dn = (hi - z) + t, (z - lo) + t
+        for k in range(K):
+            r = b * K + k
+            s = int(steps[r])
+            if not 0 <= s < nb - 1:
+                continue
+            rho = np.zeros((nb, 2))                                      # [i, a], 0 up to s
+            for c, a in enumerate(cols):
+                d = np.zeros(3)
+                for i in range(s, nb - 1):
+                    d = Abar @ d
+                    if i - s < dv.shape[1]:
+                        d[1] += dv[r, i - s, c]
+                    rho[i + 1, a] = -(d[0] - hg * d[2])
+            pos, neg = rho > 0, rho < 0
+            for col, (p, q) in enumerate(((up, dn), (dn, up))):
+                f = np.full((nb, 2), np.inf)
+                with np.errstate(over="ignore", invalid="ignore"):
+                    f[pos] = p[pos] / rho[pos]
+                    f[neg] = q[neg] / -rho[neg]
+                j = int(np.argmin(f))                    # the first minimum in (i, a) order
+                if f.flat[j] < np.inf:
+                    scale[b, k, col] = f.flat[j]
+                    limit[b, k, col] = j                 # = 2·i + a
+    return scale, limit
+
+
+class TraceMargin:
+    """The trace margins of a batch of walks with K draws each (zmpc_trace_margin): ``scale``
+    [B, K, 2] — [..., 0] the largest multiple of a draw's trace its walk survives, [..., 1] that of
+    the negated trace; +inf where no sample limits it, NaN where the walk fails undisturbed — and
+    ``limit`` [B, K, 2] int32, 2·sample + axis of what leaves its box first (−1: none).  Tensors or
+    arrays; views, no copies."""
+
+    __slots__ = ("scale", "limit")
+
+    def __init__(self, scale, limit):
+        if scale.ndim != 3 or scale.shape[2] != 2 or tuple(limit.shape) != tuple(scale.shape):
+            raise ValueError(f"scale and limit must both be [B, K, 2], got {tuple(scale.shape)} "
+                             f"and {tuple(limit.shape)}")
+        self.scale, self.limit = scale, limit
+
+    def __len__(self):
+        return int(self.scale.shape[0])
+
+    def __repr__(self):
+        return f"TraceMargin(B={len(self)}, draws={int(self.scale.shape[1])})"
+
+    @property
+    def critical(self):
+        """[B, K]: the largest multiple of each draw's trace its walk survives."""
+        return self.scale[..., 0]
+
+    @property
+    def sample(self):
+        """[B, K, 2]: the sample that leaves its box first, −1 where none does."""
+        l = self.limit
+        return (l >> 1) * (l >= 0) - (l < 0) * 1
+
+    @property
+    def axis(self):
+        """[B, K, 2]: the axis on which it leaves (0 x, 1 y), −1 where none does."""
+        l = self.limit
+        return (l & 1) * (l >= 0) - (l < 0) * 1
+
+    def survives(self, lam=1.0):
+        """[B, K] bool: does the walk survive `lam` times the draw's trace?  A negative lam asks
+        about |lam| times the negated trace (column 1).  NaN (a walk that fails undisturbed) is
+        False."""
+        lam = float(lam)
+        return self.scale[..., 1 if lam < 0 else 0] >= abs(lam)
+
+    def survival(self, lam=1.0):
+        """[B]: the fraction of a walk's draws that survive (survives(lam))."""
+        ok = self.survives(lam)
+        if hasattr(ok, "detach"):  # torch
+            return ok.to(self.scale.dtype).mean(dim=1)
+        return ok.mean(axis=1)
+
+
 def critical_force_affine(z0, r, zmax, zmin, max_violation=0.0):
     """Largest F >= 0 with zmin − max_violation <= z0 + F·r <= zmax + max_violation at every
     sample: the push an affine ZMP response survives (the unconstrained controller is linear, so

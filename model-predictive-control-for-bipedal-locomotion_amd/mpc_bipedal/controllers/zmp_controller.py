@@ -32,7 +32,7 @@ import numpy as np
 import torch
 
 from ..analysis import (NHERDT_METRICS, NMETRICS, HerdtWalkMetrics, Push, PushMap, PushTrace,
-                        WalkMetrics, check_profile, planar_push, unit_directions)
+                        TraceMargin, WalkMetrics, check_profile, planar_push, unit_directions)
 from ..config import MPCConfig
 from ..models.lipm_model import lipm_matrices
 from ..solver import get_plan
@@ -850,6 +850,45 @@ class ZMPController:
             return planar_push(force, limit, unit)[0]
         sign =torch.as_tensor(direction, dtype=torch.float64, device=dev).expand(B)
         return torch.where(sign >= 0, force[:, 0], force[:, 1])
+
+    def trace_margin(self, z_max, z_min, trace: PushTrace, x_init=None, walk_lengths=None,
+                     max_violation: float = 1e-9, draws: int = 1) -> TraceMargin:
+        """The largest multiple of its trace each (walk, draw) survives, in closed form (addition;
+        zmpc_trace_margin): one unpushed rollout of the B walks, then one launch over the
+        B·draws rows of `trace` — no rollout per evaluation and no history per draw.  Row
+        b·draws + k of the trace is the k-th disturbance draw of walk b, so many random draws
+        per nominal walk cost one rollout; TraceMargin.survival() is then the fraction of a walk's
+        draws it survives.
+
+        z_max, z_min [B,n,2] or a shared [n,2]; x_init [B,2,3] or None; walk_lengths [B] live
+        samples of ragged walks; trace: an analysis.PushTrace with B·draws rows (ValueError
+        otherwise).  Returns analysis.TraceMargin on the device: scale [B, draws, 2] ([..., 0]
+        the trace, [..., 1] the negated trace; +inf where no sample limits it, NaN where the walk
+        fails undisturbed) and limit [B, draws, 2].  Only the ZMP criterion (max_violation), and
+        unconstrained plans only: a strict plan raises RuntimeError.  critical_force(trace=)
+        remains for what this cannot answer — strict plans, whose clamped response is not affine
+        in the scale, and the CoM and DCM criteria (max_com_dev, max_dcm_end)."""
+        if not isinstance(trace, PushTrace):
+            raise ValueError(f"trace must be an analysis.PushTrace, got {type(trace).__name__}")
+        if isinstance(draws, bool) or not isinstance(draws, (int, np.integer)) or draws < 1:
+            raise ValueError(f"draws must be an integer >= 1, got {draws!r}")
+        if trace.batch() % int(draws):
+            raise ValueError(f"the trace holds {trace.batch()} rows, not a multiple of draws = "
+                             f"{draws} (row b·draws + k is draw k of walk b)")
+        # the walks the other arguments name (as _scenario counts them), else the trace's own
+        walks = trace.batch() // int(draws)
+        named = np.shape(x_init)[0] if x_init is not None else \
+            (np.shape(z_max)[0] if np.ndim(z_max) == 3 else walks)
+        if named != walks:
+            raise ValueError(f"the trace holds {trace.batch()} rows, B·draws = {named}·{draws} = "
+                             f"{named * int(draws)} are needed (row b·draws + k is draw k of "
+                             "walk b)")
+        plan, hist, zmax_t, zmin_t, lengths, _, _ = self._unpushed(
+            z_max, z_min, x_init, walk_lengths, extra=(np.empty(walks),))
+        scale, limit = plan.trace_margin(hist, zmax_t, zmin_t, trace, draws=int(draws),
+                                         lengths=lengths, max_violation=max_violation,
+                                         mass=self.config.m)
+        return TraceMargin(scale, limit)
 
     # ------------------------------------------------------------------ internals
     def _rollout_host(self, x_init, y_init, z_max, z_min, kick, kick_step) -> np.ndarray:

@@ -458,6 +458,41 @@ class Plan:
             _native.call("zmpc_push_map", self.device, *walks, *outs)
         return (force, limit, resp) if want_response else (force, limit)
 
+    # -- trace margin (zmpc_trace_margin) --------------------------------------------------
+    def trace_margin(self, hist, zmax, zmin, trace, draws=1, lengths=None, max_violation=1e-9,
+                     mass=None, scale=None, limit=None):
+        """Exact critical scale of every (walk, draw) row's trace from an unpushed state history
+        (zmpc_trace_margin, include/zmpc.h) → (scale [B, K, 2] float64, limit [B, K, 2] int32) on
+        the device.  scale[b, k, 0] is the largest multiple of draw k's trace walk b survives,
+        [..., 1] that of the negated trace; limit holds 2·i + a of the sample and axis that leaves
+        first, −1 where none does (+inf) or the walk fails undisturbed (NaN).
+
+        hist, zmax, zmin, lengths: as walk_metrics.  trace: an analysis.PushTrace of B·draws rows,
+        row b·draws + k the k-th draw of walk b (ValueError when trace.batch() != B·draws); a
+        trace in newtons needs mass, as rollout.  scale, limit: contiguous tensors of those shapes
+        on the plan's device to write into.  Asynchronous on the current stream.  Non-strict
+        plans only: a strict plan raises NativeError (ZMPC_ESTATE)."""
+        B, n = self._hist_dims(hist)
+        if isinstance(draws, bool) or not isinstance(draws, (int, np.integer)) or draws < 1:
+            raise ValueError(f"draws must be an integer >= 1, got {draws!r}")
+        K = int(draws)
+        zmax, zmin, bstride = self._bounds(zmax, zmin, B, n)
+        len_t = self._index(lengths, B, "lengths")
+        from .analysis import PushTrace
+        if isinstance(trace, PushTrace) and trace.batch() != B * K:
+            raise ValueError(f"the trace holds {trace.batch()} rows, B·draws = {B}·{K} = {B * K} "
+                             "are needed (row b·draws + k is draw k of walk b)")
+        traced = self._trace_struct(trace, mass, B * K)
+        msg = (f"scale and limit must be (float64, int32) contiguous {(B, K, 2)} tensors on the "
+               "plan's device")
+        scale = self._out(scale, (B, K, 2), torch.float64, msg)
+        limit = self._out(limit, (B, K, 2), torch.int32, msg)
+        _native.call_traced("zmpc_trace_margin", self.device, traced.struct, self._live(), B, n,
+                            _ptr(hist), _ptr(zmax), _ptr(zmin), bstride, _ptr(len_t), K,
+                            ctypes.addressof(traced.struct), float(max_violation), _ptr(scale),
+                            _ptr(limit))
+        return scale, limit
+
     # -- fused rollout-to-metrics (zmpc_rollout_metrics) -----------------------------------
     def _rollout_metrics_args(self, zmax, zmin, x0, kick, kick_step, lengths, out, status):
         zmax, zmin, x0, B, n, bstride = self._walk_inputs(zmax, zmin, x0)
