@@ -57,6 +57,22 @@ void free_plan(zmpc_plan* p) {
   delete p;
 }
 
+// The checks several entry points state in the same words; each entry point applies them in its
+// own order (`if (int rc = need_…) return rc;`)
+int need_walks(int64_t B, int64_t n) {
+  return B < 0 || n < 1 ? fail(ZMPC_EINVAL, "need B >= 0 and n >= 1") : ZMPC_OK;
+}
+int need_bounds_stride(int64_t stride, int64_t n) {
+  if (stride == 0 || stride >= 2 * n) return ZMPC_OK;
+  return fail(ZMPC_EINVAL, "bounds_stride must be 0 (shared CoP) or >= 2n");
+}
+int need_batch(int64_t B) {
+  return B > 0x7fffffff ? fail(ZMPC_EINVAL, "batch too large") : ZMPC_OK;
+}
+int need_length(int64_t n) {
+  return n > (1 << 24) ? fail(ZMPC_EINVAL, "walk too long") : ZMPC_OK;
+}
+
 // per-device one-time kernel attributes and pool threshold; plan creation may run on several
 // host threads at once (zmpc.h: plans are shareable across threads), so the check-and-set is
 // under a lock
@@ -360,21 +376,6 @@ static bool push_is_kick(const zmpc_push* push) {
   return push->axes == ZMPC_PUSH_AXIS_Y && push->duration == 1 && push->profile == nullptr;
 }
 
-// A checked zmpc_push as the launchers take it, in a walk of n samples
-static PushArgs push_args(const zmpc_push* push, int64_t n) {
-  PushArgs w{};
-  w.amp = push->amp;
-  w.w = push->profile;
-  w.steps = push->steps;
-  w.step = push->step;
-  w.dur = (int)(push->duration < n ? push->duration : n);
-  w.cols = push->axes == (ZMPC_PUSH_AXIS_X | ZMPC_PUSH_AXIS_Y) ? 2 : 1;
-  w.col[0] = (push->axes & ZMPC_PUSH_AXIS_X) ? 0 : -1;
-  w.col[1] = (push->axes & ZMPC_PUSH_AXIS_Y) ? w.cols - 1 : -1;
-  w.astride = w.cols;
-  return w;
-}
-
 // The checks of a zmpc_trace (include/zmpc.h "The trace, stated once"), before any device call
 static int trace_check(const zmpc_trace* trace, int64_t B) {
   if (!trace) return fail(ZMPC_EINVAL, "trace is NULL");
@@ -388,100 +389,124 @@ static int trace_check(const zmpc_trace* trace, int64_t B) {
   return ZMPC_OK;
 }
 
-// A checked zmpc_trace as the launchers take it, in a walk of n samples: the window of L steps
-// whose value is read from the walk's own row
-static PushArgs trace_args(const zmpc_trace* trace, int64_t n) {
+// What disturbs the walks of a rollout, resolved once by the entry point: nothing or the
+// one-sample y kick of the call's own kick fields (push all zero), a push window, or a trace
+struct Disturbance {
+  enum Kind { Kick, Window, Trace } kind;
+  PushArgs push;     // as the launchers take it
+  int64_t L;         // a trace's samples per walk as the caller gave them (push.dur is clamped)
+  void* stream;
+  const char* name;  // the entry point, for messages
+};
+
+// The window of `len` steps on `axes` in a walk of n samples: the axes-to-columns rule
+static PushArgs window_args(const double* amp, int32_t axes, const int64_t* steps, int64_t step,
+                            int64_t len, int64_t n) {
   PushArgs w{};
-  w.amp = trace->dv;
-  w.steps = trace->steps;
-  w.step = trace->step;
-  w.dur = (int)(trace->length < n ? trace->length : n);
-  w.cols = trace->axes == (ZMPC_PUSH_AXIS_X | ZMPC_PUSH_AXIS_Y) ? 2 : 1;
-  w.col[0] = (trace->axes & ZMPC_PUSH_AXIS_X) ? 0 : -1;
-  w.col[1] = (trace->axes & ZMPC_PUSH_AXIS_Y) ? w.cols - 1 : -1;
-  w.tstride = w.cols;
-  w.astride = trace->length * w.cols;
+  w.amp = amp;
+  w.steps = steps;
+  w.step = step;
+  w.dur = (int)(len < n ? len : n);
+  w.cols = axes == (ZMPC_PUSH_AXIS_X | ZMPC_PUSH_AXIS_Y) ? 2 : 1;
+  w.col[0] = (axes & ZMPC_PUSH_AXIS_X) ? 0 : -1;
+  w.col[1] = (axes & ZMPC_PUSH_AXIS_Y) ? w.cols - 1 : -1;
+  w.astride = w.cols;
   return w;
 }
 
-// zmpc_rollout, zmpc_rollout_kicks and, with a push window (kick is NULL then), the general
-// zmpc_rollout_pushed; with a trace (kick and push are NULL then), zmpc_rollout_traced
-static int rollout_impl(const zmpc_plan* P, int64_t B, int64_t n, const double* zmax,
-                        const double* zmin, int64_t bounds_stride, const double* x0,
-                        const double* kick, int64_t kick_step, const int64_t* kick_steps,
-                        const zmpc_push* push, double* hist, int32_t* status, void* stream,
-                        const zmpc_trace* trace = nullptr) {
+static Disturbance kick_of(void* stream, const char* name) {
+  return {Disturbance::Kick, PushArgs{}, 0, stream, name};
+}
+
+// A checked zmpc_push in a walk of n samples
+static Disturbance window_of(const zmpc_push* p, int64_t n, void* stream, const char* name) {
+  Disturbance d{Disturbance::Window,
+                window_args(p->amp, p->axes, p->steps, p->step, p->duration, n), 0, stream, name};
+  d.push.w = p->profile;
+  return d;
+}
+
+// A checked zmpc_trace in a walk of n samples: the window of L steps whose value is read from
+// the walk's own row
+static Disturbance trace_of(const zmpc_trace* t, int64_t n, const char* name) {
+  Disturbance d{Disturbance::Trace, window_args(t->dv, t->axes, t->steps, t->step, t->length, n),
+                t->length, t->stream, name};
+  d.push.tstride = d.push.cols;
+  d.push.astride = t->length * d.push.cols;
+  return d;
+}
+
+// What the reduced-Cholesky strict kernels take instead of a window and of a trace: the tails of
+// the two refusals below, by Disturbance::Kind
+static const char* const kCholTakes[3][2] = {
+    {nullptr, nullptr},
+    {"takes the one-sample y push alone",
+     "take the one-sample y push alone (the y axis, duration 1, no profile); "},
+    {"takes no trace", "take no trace; "}};
+
+// A filled call of zmpc_rollout, zmpc_rollout_kicks, zmpc_rollout_pushed (a push that is the
+// legacy kick arrives as the kick) or zmpc_rollout_traced, under its disturbance
+static int rollout_impl(const zmpc_plan* P, RolloutCall c, const Disturbance& d) {
   g_err.clear();
   if (!P) return fail(ZMPC_EINVAL, "NULL plan");
-  if (B < 0 || n < 1) return fail(ZMPC_EINVAL, "need B >= 0 and n >= 1");
-  if (B == 0) return ZMPC_OK;
-  if (!zmax || !zmin || !x0 || !hist) return fail(ZMPC_EINVAL, "NULL array argument");
-  if (B > 0x7fffffff) return fail(ZMPC_EINVAL, "batch too large");
-  if (n > (1 << 24)) return fail(ZMPC_EINVAL, "walk too long");
-  if (bounds_stride != 0 && bounds_stride < 2 * n)
-    return fail(ZMPC_EINVAL, "bounds_stride must be 0 (shared CoP) or >= 2n");
-  if (trace && P->strict) {
+  if (int rc = need_walks(c.B, c.n)) return rc;
+  if (c.B == 0) return ZMPC_OK;
+  if (!c.zmax || !c.zmin || !c.x0 || !c.hist) return fail(ZMPC_EINVAL, "NULL array argument");
+  if (int rc = need_batch(c.B)) return rc;
+  if (int rc = need_length(c.n)) return rc;
+  if (int rc = need_bounds_stride(c.bstride, c.n)) return rc;
+  if (d.kind != Disturbance::Kick && P->strict) {
     // refused before any device call, nothing is launched
     const StrictKind kind =
-        choose_strict(P->N, 2 * B, P->opt[ZMPC_OPT_STRICT_SOLVER], P->lqtab != nullptr);
+        choose_strict(P->N, 2 * c.B, P->opt[ZMPC_OPT_STRICT_SOLVER], P->lqtab != nullptr);
     if (kind == StrictKind::Tile && P->opt[ZMPC_OPT_STRICT_SOLVER] == 0)
       return fail(ZMPC_ESTATE,
-                  "zmpc_rollout_traced: at horizon N = " + std::to_string(P->N) +
+                  std::string(d.name) + ": at horizon N = " + std::to_string(P->N) +
                       " neither the LQ nor the parallel-in-time strict kernel runs, and the "
-                      "reduced-Cholesky kernel left takes no trace");
+                      "reduced-Cholesky kernel left " + kCholTakes[d.kind][0]);
     if (kind == StrictKind::Tile || kind == StrictKind::Wave)
       return fail(ZMPC_ESTATE,
-                  "zmpc_rollout_traced: the reduced-Cholesky strict kernels (strict solver options "
-                  "1 and 2) take no trace; use strict solver 0, 3 or 4");
-  }
-  if (push && P->strict) {
-    // refused before any device call, nothing is launched
-    const StrictKind kind =
-        choose_strict(P->N, 2 * B, P->opt[ZMPC_OPT_STRICT_SOLVER], P->lqtab != nullptr);
-    if (kind == StrictKind::Tile && P->opt[ZMPC_OPT_STRICT_SOLVER] == 0)
-      return fail(ZMPC_ESTATE,
-                  "zmpc_rollout_pushed: at horizon N = " + std::to_string(P->N) +
-                      " neither the LQ nor the parallel-in-time strict kernel runs, and the "
-                      "reduced-Cholesky kernel left takes the one-sample y push alone");
-    if (kind == StrictKind::Tile || kind == StrictKind::Wave)
-      return fail(ZMPC_ESTATE,
-                  "zmpc_rollout_pushed: the reduced-Cholesky strict kernels (strict solver options "
-                  "1 and 2) take the one-sample y push alone (the y axis, duration 1, no profile); "
-                  "use strict solver 0, 3 or 4");
+                  std::string(d.name) + ": the reduced-Cholesky strict kernels (strict solver "
+                      "options 1 and 2) " + kCholTakes[d.kind][1] + "use strict solver 0, 3 or 4");
   }
   DeviceGuard g(P->device);
   if (g.err != hipSuccess) return hip_fail(g.err, "hipSetDevice");
   std::string why;
-  hipStream_t s = (hipStream_t)stream;
-  RolloutCall c{B, n, zmax, zmin, bounds_stride, x0, kick, kick_step, kick_steps, hist, status};
+  hipStream_t s = (hipStream_t)d.stream;
   hipError_t e;
   if (P->strict) {
-    if (push) c.push = push_args(push, n);
-    if (trace) c.push = trace_args(trace, n);
+    c.push = d.push;
     e = zmpc_launch_rollout_strict(P, c, s, &why);
   } else {
-    // (unconstrained: the unpushed rollout, then the window's linear state response)
+    // (unconstrained: the unpushed rollout, then the window's linear state response, or the
+    // scan of the walk's own trace, trace.hip)
     e = zmpc_launch_rollout_unc(P, c, s, &why);
-    if (push && e == hipSuccess) {
-      c.push = push_args(push, n);
-      e = zmpc_launch_push_response(P, c, s);
-    }
-    // (a trace: the unpushed rollout, then the scan of the walk's own trace, trace.hip)
-    if (trace && e == hipSuccess) {
-      c.push = trace_args(trace, n);
-      e = zmpc_launch_trace_response(P, c, trace->length, s);
+    if (d.kind != Disturbance::Kick && e == hipSuccess) {
+      c.push = d.push;
+      e = d.kind == Disturbance::Trace ? zmpc_launch_trace_response(P, c, d.L, s)
+                                       : zmpc_launch_push_response(P, c, s);
     }
   }
-  return launch_result(e, why,
-                       trace ? "zmpc_rollout_traced" : push ? "zmpc_rollout_pushed" : "zmpc_rollout");
+  return launch_result(e, why, d.name);
+}
+
+// The walks of a rollout call: no kick, no push
+static RolloutCall rollout_walks(int64_t B, int64_t n, const double* zmax, const double* zmin,
+                                 int64_t bounds_stride, const double* x0, double* hist,
+                                 int32_t* status) {
+  RolloutCall c{};
+  c.B = B, c.n = n, c.zmax = zmax, c.zmin = zmin, c.bstride = bounds_stride, c.x0 = x0;
+  c.kick_step = -1, c.hist = hist, c.status = status;
+  return c;
 }
 
 int zmpc_rollout(const zmpc_plan* P, int64_t B, int64_t n, const double* zmax,
                  const double* zmin, int64_t bounds_stride, const double* x0,
                  const double* kick, int64_t kick_step, double* hist, int32_t* status,
                  void* stream) {
-  return rollout_impl(P, B, n, zmax, zmin, bounds_stride, x0, kick, kick_step, nullptr, nullptr,
-                      hist, status, stream);
+  RolloutCall c = rollout_walks(B, n, zmax, zmin, bounds_stride, x0, hist, status);
+  c.kick = kick, c.kick_step = kick_step;
+  return rollout_impl(P, c, kick_of(stream, "zmpc_rollout"));
 }
 
 int zmpc_rollout_kicks(const zmpc_plan* P, int64_t B, int64_t n, const double* zmax,
@@ -492,8 +517,9 @@ int zmpc_rollout_kicks(const zmpc_plan* P, int64_t B, int64_t n, const double* z
     g_err.clear();
     return fail(ZMPC_EINVAL, "kick_steps is NULL (use zmpc_rollout for one kick step)");
   }
-  return rollout_impl(P, B, n, zmax, zmin, bounds_stride, x0, kick, -1, kick_steps, nullptr, hist,
-                      status, stream);
+  RolloutCall c = rollout_walks(B, n, zmax, zmin, bounds_stride, x0, hist, status);
+  c.kick = kick, c.kick_steps = kick_steps;
+  return rollout_impl(P, c, kick_of(stream, "zmpc_rollout"));
 }
 
 int zmpc_rollout_pushed(const zmpc_plan* P, int64_t B, int64_t n, const double* zmax,
@@ -501,13 +527,14 @@ int zmpc_rollout_pushed(const zmpc_plan* P, int64_t B, int64_t n, const double* 
                         const zmpc_push* push, double* hist, int32_t* status, void* stream) {
   g_err.clear();
   if (!P) return fail(ZMPC_EINVAL, "NULL plan");
-  const int rc = push_check(push, B);
-  if (rc != ZMPC_OK) return rc;
-  if (push_is_kick(push))  // what users get today, on every plan kind
-    return rollout_impl(P, B, n, zmax, zmin, bounds_stride, x0, push->amp,
-                        push->steps ? -1 : push->step, push->steps, nullptr, hist, status, stream);
-  return rollout_impl(P, B, n, zmax, zmin, bounds_stride, x0, nullptr, -1, nullptr, push, hist,
-                      status, stream);
+  if (int rc = push_check(push, B)) return rc;
+  RolloutCall c = rollout_walks(B, n, zmax, zmin, bounds_stride, x0, hist, status);
+  if (!push_is_kick(push))
+    return rollout_impl(P, c, window_of(push, n, stream, "zmpc_rollout_pushed"));
+  // what users get today, on every plan kind: the kick path, under its name
+  c.kick = push->amp, c.kick_steps = push->steps;
+  if (!push->steps) c.kick_step = push->step;
+  return rollout_impl(P, c, kick_of(stream, "zmpc_rollout"));
 }
 
 int zmpc_rollout_traced(const zmpc_plan* P, int64_t B, int64_t n, const double* zmax,
@@ -515,10 +542,9 @@ int zmpc_rollout_traced(const zmpc_plan* P, int64_t B, int64_t n, const double* 
                         const zmpc_trace* trace, double* hist, int32_t* status) {
   g_err.clear();
   if (!P) return fail(ZMPC_EINVAL, "NULL plan");
-  const int rc = trace_check(trace, B);
-  if (rc != ZMPC_OK) return rc;
-  return rollout_impl(P, B, n, zmax, zmin, bounds_stride, x0, nullptr, -1, nullptr, nullptr, hist,
-                      status, trace->stream, trace);
+  if (int rc = trace_check(trace, B)) return rc;
+  return rollout_impl(P, rollout_walks(B, n, zmax, zmin, bounds_stride, x0, hist, status),
+                      trace_of(trace, n, "zmpc_rollout_traced"));
 }
 
 int zmpc_walk_metrics(const zmpc_plan* P, int64_t B, int64_t n, const double* hist,
@@ -526,13 +552,12 @@ int zmpc_walk_metrics(const zmpc_plan* P, int64_t B, int64_t n, const double* hi
                       const int64_t* lengths, double* metrics, void* stream) {
   g_err.clear();
   if (!P) return fail(ZMPC_EINVAL, "NULL plan");
-  if (B < 0 || n < 1) return fail(ZMPC_EINVAL, "need B >= 0 and n >= 1");
-  if (bounds_stride != 0 && bounds_stride < 2 * n)
-    return fail(ZMPC_EINVAL, "bounds_stride must be 0 (shared CoP) or >= 2n");
+  if (int rc = need_walks(B, n)) return rc;
+  if (int rc = need_bounds_stride(bounds_stride, n)) return rc;
   if (B == 0) return ZMPC_OK;
   if (!hist || !zmax || !zmin || !metrics) return fail(ZMPC_EINVAL, "NULL array argument");
-  if (B > 0x7fffffff) return fail(ZMPC_EINVAL, "batch too large");
-  if (n > (1 << 24)) return fail(ZMPC_EINVAL, "walk too long");
+  if (int rc = need_batch(B)) return rc;
+  if (int rc = need_length(n)) return rc;
   DeviceGuard g(P->device);
   if (g.err != hipSuccess) return hip_fail(g.err, "hipSetDevice");
   hipError_t e = zmpc_launch_walk_metrics(P, B, n, hist, zmax, zmin, bounds_stride, lengths,
@@ -547,13 +572,12 @@ int zmpc_rollout_metrics(const zmpc_plan* P, int64_t B, int64_t n, const double*
                          const int64_t* lengths, double* metrics, int32_t* status, void* stream) {
   g_err.clear();
   if (!P) return fail(ZMPC_EINVAL, "NULL plan");
-  if (B < 0 || n < 1) return fail(ZMPC_EINVAL, "need B >= 0 and n >= 1");
-  if (bounds_stride != 0 && bounds_stride < 2 * n)
-    return fail(ZMPC_EINVAL, "bounds_stride must be 0 (shared CoP) or >= 2n");
+  if (int rc = need_walks(B, n)) return rc;
+  if (int rc = need_bounds_stride(bounds_stride, n)) return rc;
   if (B > 0 && (!zmax || !zmin || !x0 || !metrics))
     return fail(ZMPC_EINVAL, "NULL array argument");
-  if (B > 0x7fffffff) return fail(ZMPC_EINVAL, "batch too large");
-  if (n > (1 << 24)) return fail(ZMPC_EINVAL, "walk too long");
+  if (int rc = need_batch(B)) return rc;
+  if (int rc = need_length(n)) return rc;
   // the shapes without a fused form: refused before any device call, nothing is launched
   if (P->strict)
     return fail(ZMPC_ESTATE, "zmpc_rollout_metrics: strict plans have no fused form (use "
@@ -567,8 +591,8 @@ int zmpc_rollout_metrics(const zmpc_plan* P, int64_t B, int64_t n, const double*
   if (B == 0) return ZMPC_OK;
   DeviceGuard g(P->device);
   if (g.err != hipSuccess) return hip_fail(g.err, "hipSetDevice");
-  const RolloutCall rc{B, n, zmax, zmin, bounds_stride, x0, kick, kick_step, kick_steps, nullptr,
-                       status};
+  RolloutCall rc = rollout_walks(B, n, zmax, zmin, bounds_stride, x0, nullptr, status);
+  rc.kick = kick, rc.kick_step = kick_step, rc.kick_steps = kick_steps;
   const hipError_t e =
       zmpc_launch_rollout_metrics(P, rc, lengths, metrics, (hipStream_t)stream);
   return launch_result(e, std::string(), "zmpc_rollout_metrics");
@@ -580,19 +604,18 @@ static int push_map_impl(const char* name, bool shaped, const zmpc_plan* P, cons
                          void* stream) {
   g_err.clear();
   if (!P) return fail(ZMPC_EINVAL, "NULL plan");
-  if (c.B < 0 || c.n < 1) return fail(ZMPC_EINVAL, "need B >= 0 and n >= 1");
+  if (int rc = need_walks(c.B, c.n)) return rc;
   if (!(c.t >= 0)) return fail(ZMPC_EINVAL, "need max_violation >= 0");
   if (!(c.mass > 0) || !(c.mass < __builtin_inf()))
     return fail(ZMPC_EINVAL, "need a finite mass > 0");
-  if (c.bstride != 0 && c.bstride < 2 * c.n)
-    return fail(ZMPC_EINVAL, "bounds_stride must be 0 (shared CoP) or >= 2n");
+  if (int rc = need_bounds_stride(c.bstride, c.n)) return rc;
   if (c.duration < 1) return fail(ZMPC_EINVAL, "need duration >= 1 (samples)");
   if (c.axes < 1 || c.axes > (ZMPC_PUSH_AXIS_X | ZMPC_PUSH_AXIS_Y))
     return fail(ZMPC_EINVAL, "axes must be 1 (the x axis), 2 (the y axis) or 3 (both)");
   if (c.B > 0 && (!c.hist || !c.zmax || !c.zmin || !c.force))
     return fail(ZMPC_EINVAL, "NULL array argument");
-  if (c.B > 0x7fffffff) return fail(ZMPC_EINVAL, "batch too large");
-  if (c.n > (1 << 24)) return fail(ZMPC_EINVAL, "walk too long");
+  if (int rc = need_batch(c.B)) return rc;
+  if (int rc = need_length(c.n)) return rc;
   // refused before any device call, nothing is launched
   if (P->strict)
     return fail(ZMPC_ESTATE, std::string(name) +
@@ -638,14 +661,12 @@ int zmpc_trace_margin(const zmpc_plan* P, int64_t B, int64_t n, const double* hi
                       double max_violation, double* scale, int32_t* limit) {
   g_err.clear();
   if (!P) return fail(ZMPC_EINVAL, "NULL plan");
-  if (B < 0 || n < 1) return fail(ZMPC_EINVAL, "need B >= 0 and n >= 1");
+  if (int rc = need_walks(B, n)) return rc;
   if (draws < 1) return fail(ZMPC_EINVAL, "need draws >= 1 (traces per walk)");
   if (B > 0x7fffffff / draws) return fail(ZMPC_EINVAL, "batch too large (B * draws rows)");
-  const int rc = trace_check(trace, B * draws);
-  if (rc != ZMPC_OK) return rc;
+  if (int rc = trace_check(trace, B * draws)) return rc;
   if (!(max_violation >= 0)) return fail(ZMPC_EINVAL, "need max_violation >= 0");
-  if (bounds_stride != 0 && bounds_stride < 2 * n)
-    return fail(ZMPC_EINVAL, "bounds_stride must be 0 (shared CoP) or >= 2n");
+  if (int rc = need_bounds_stride(bounds_stride, n)) return rc;
   if (B > 0 && (!hist || !zmax || !zmin || !scale))
     return fail(ZMPC_EINVAL, "NULL array argument");
   // (no LDS per sample, so none of the rollouts' 2^24; limit holds 2·i + a in an int32)
@@ -659,10 +680,11 @@ int zmpc_trace_margin(const zmpc_plan* P, int64_t B, int64_t n, const double* hi
   if (B == 0) return ZMPC_OK;
   DeviceGuard g(P->device);
   if (g.err != hipSuccess) return hip_fail(g.err, "hipSetDevice");
-  const MarginCall c{B,     n,     hist,          zmax,          zmin,  bounds_stride, lengths,
-                     draws, trace_args(trace, n), trace->length, max_violation, scale, limit};
-  return launch_result(zmpc_launch_trace_margin(P, c, (hipStream_t)trace->stream), std::string(),
-                       "zmpc_trace_margin");
+  const Disturbance d = trace_of(trace, n, "zmpc_trace_margin");
+  const MarginCall c{B,     n,      hist, zmax,          zmin,  bounds_stride, lengths,
+                     draws, d.push, d.L,  max_violation, scale, limit};
+  return launch_result(zmpc_launch_trace_margin(P, c, (hipStream_t)d.stream), std::string(),
+                       d.name);
 }
 
 static int herdt_check(const zmpc_plan* P, const zmpc_herdt_params* prm, int64_t B) {
@@ -681,11 +703,10 @@ static int herdt_check(const zmpc_plan* P, const zmpc_herdt_params* prm, int64_t
   return ZMPC_OK;
 }
 
-// zmpc_herdt_rollout and zmpc_herdt_rollout_pushed: the checks of a filled call, and its launch
-static int herdt_rollout_impl(const zmpc_plan* P, const zmpc_herdt_params* prm, const HerdtCall& c,
-                              void* stream, const char* name) {
-  int rc = herdt_check(P, prm, c.B);
-  if (rc != ZMPC_OK) return rc;
+// A filled call of the three Herdt rollouts under its disturbance: its checks, and its launch
+static int herdt_rollout_impl(const zmpc_plan* P, const zmpc_herdt_params* prm, HerdtCall c,
+                              const Disturbance& d) {
+  if (int rc = herdt_check(P, prm, c.B)) return rc;
   if (c.n < 1) return fail(ZMPC_EINVAL, "need n >= 1");
   if (c.B == 0) return ZMPC_OK;
   if (!c.vref || !c.st || !c.nb || !c.x0 || !c.hist || !c.foot)
@@ -695,13 +716,26 @@ static int herdt_rollout_impl(const zmpc_plan* P, const zmpc_herdt_params* prm, 
     return fail(ZMPC_EINVAL, "strides must be 0 (shared) or cover a whole walk");
   DeviceGuard g(P->device);
   if (g.err != hipSuccess) return hip_fail(g.err, "hipSetDevice");
-  hipStream_t s = (hipStream_t)stream;
+  hipStream_t s = (hipStream_t)d.stream;
   if (c.status) {
     hipError_t e = hipMemsetAsync(c.status, 0, sizeof(int32_t) * c.B, s);
     if (e != hipSuccess) return hip_fail(e, "hipMemsetAsync");
   }
+  c.push = d.push;
   std::string why;
-  return launch_result(zmpc_launch_herdt_rollout(P, prm, c, s, &why), why, name);
+  return launch_result(zmpc_launch_herdt_rollout(P, prm, c, s, &why), why, d.name);
+}
+
+// The walks of a Herdt rollout call: no kick, no push
+static HerdtCall herdt_walks(int64_t B, int64_t n, const double* v_ref, int64_t v_stride,
+                             const int8_t* states, int64_t s_stride, const int32_t* nb_next,
+                             int64_t nb_stride, const double* x0, double* hist, double* foot,
+                             int32_t* status) {
+  HerdtCall c{};
+  c.B = B, c.n = n, c.vref = v_ref, c.vs = v_stride, c.st = states, c.ss = s_stride;
+  c.nb = nb_next, c.ns = nb_stride, c.x0 = x0, c.kick_step = -1;
+  c.hist = hist, c.foot = foot, c.status = status;
+  return c;
 }
 
 int zmpc_herdt_rollout(const zmpc_plan* P, const zmpc_herdt_params* prm, int64_t B, int64_t n,
@@ -710,9 +744,10 @@ int zmpc_herdt_rollout(const zmpc_plan* P, const zmpc_herdt_params* prm, int64_t
                        const double* x0, const double* kick, int64_t kick_step, double* hist,
                        double* foot, int32_t* status, void* stream) {
   g_err.clear();
-  const HerdtCall c{B, n, v_ref, v_stride, states, s_stride, nb_next, nb_stride, x0, kick,
-                    kick_step, PushArgs{}, hist, foot, status};
-  return herdt_rollout_impl(P, prm, c, stream, "zmpc_herdt_rollout");
+  HerdtCall c = herdt_walks(B, n, v_ref, v_stride, states, s_stride, nb_next, nb_stride, x0, hist,
+                            foot, status);
+  c.kick = kick, c.kick_step = kick_step;
+  return herdt_rollout_impl(P, prm, c, kick_of(stream, "zmpc_herdt_rollout"));
 }
 
 int zmpc_herdt_rollout_pushed(const zmpc_plan* P, const zmpc_herdt_params* prm, int64_t B,
@@ -722,18 +757,15 @@ int zmpc_herdt_rollout_pushed(const zmpc_plan* P, const zmpc_herdt_params* prm, 
                               double* hist, double* foot, int32_t* status, void* stream) {
   g_err.clear();
   if (!P || !prm) return fail(ZMPC_EINVAL, "NULL plan or params");
-  const int rc = push_check(push, B);
-  if (rc != ZMPC_OK) return rc;
-  if (push_is_kick(push) && !push->steps)  // what users get today: zmpc_herdt_rollout's kick
-    return zmpc_herdt_rollout(P, prm, B, n, v_ref, v_stride, states, s_stride, nb_next, nb_stride,
-                              x0, push->amp, push->step, hist, foot, status, stream);
-  HerdtCall c{B, n, v_ref, v_stride, states, s_stride, nb_next, nb_stride, x0};
-  c.kick_step = -1;
-  c.push = push_args(push, n);
-  c.hist = hist;
-  c.foot = foot;
-  c.status = status;
-  return herdt_rollout_impl(P, prm, c, stream, "zmpc_herdt_rollout_pushed");
+  if (int rc = push_check(push, B)) return rc;
+  HerdtCall c = herdt_walks(B, n, v_ref, v_stride, states, s_stride, nb_next, nb_stride, x0, hist,
+                            foot, status);
+  if (!push_is_kick(push) || push->steps)
+    return herdt_rollout_impl(P, prm, c,
+                              window_of(push, n, stream, "zmpc_herdt_rollout_pushed"));
+  // what users get today: zmpc_herdt_rollout's kick, under its name
+  c.kick = push->amp, c.kick_step = push->step;
+  return herdt_rollout_impl(P, prm, c, kick_of(stream, "zmpc_herdt_rollout"));
 }
 
 int zmpc_herdt_rollout_traced(const zmpc_plan* P, const zmpc_herdt_params* prm, int64_t B,
@@ -743,15 +775,11 @@ int zmpc_herdt_rollout_traced(const zmpc_plan* P, const zmpc_herdt_params* prm, 
                               double* hist, double* foot, int32_t* status) {
   g_err.clear();
   if (!P || !prm) return fail(ZMPC_EINVAL, "NULL plan or params");
-  const int rc = trace_check(trace, B);
-  if (rc != ZMPC_OK) return rc;
-  HerdtCall c{B, n, v_ref, v_stride, states, s_stride, nb_next, nb_stride, x0};
-  c.kick_step = -1;
-  c.push = trace_args(trace, n < 1 ? 1 : n);
-  c.hist = hist;
-  c.foot = foot;
-  c.status = status;
-  return herdt_rollout_impl(P, prm, c, trace->stream, "zmpc_herdt_rollout_traced");
+  if (int rc = trace_check(trace, B)) return rc;
+  return herdt_rollout_impl(P, prm,
+                            herdt_walks(B, n, v_ref, v_stride, states, s_stride, nb_next,
+                                        nb_stride, x0, hist, foot, status),
+                            trace_of(trace, n < 1 ? 1 : n, "zmpc_herdt_rollout_traced"));
 }
 
 int zmpc_herdt_walk_metrics(const zmpc_plan* P, const zmpc_herdt_params* prm, int64_t B,
@@ -761,7 +789,7 @@ int zmpc_herdt_walk_metrics(const zmpc_plan* P, const zmpc_herdt_params* prm, in
                             double* metrics, void* stream) {
   g_err.clear();
   if (!P || !prm) return fail(ZMPC_EINVAL, "NULL plan or params");
-  if (B < 0 || n < 1) return fail(ZMPC_EINVAL, "need B >= 0 and n >= 1");
+  if (int rc = need_walks(B, n)) return rc;
   if (!(count_tol >= 0)) return fail(ZMPC_EINVAL, "need count_tol >= 0");
   for (int sd = 0; sd < 2; ++sd)
     if (prm->nfacets[sd] < 0 || prm->nfacets[sd] > ZMPC_HERDT_MAX_FACETS)
@@ -770,8 +798,8 @@ int zmpc_herdt_walk_metrics(const zmpc_plan* P, const zmpc_herdt_params* prm, in
     return fail(ZMPC_EINVAL, "s_stride must be 0 (shared) or >= n, foot_ref_stride 0 or >= 2n");
   if (B > 0 && (!hist || !foot || !states || !metrics))
     return fail(ZMPC_EINVAL, "NULL array argument");
-  if (B > 0x7fffffff) return fail(ZMPC_EINVAL, "batch too large");
-  if (n > (1 << 24)) return fail(ZMPC_EINVAL, "walk too long");
+  if (int rc = need_batch(B)) return rc;
+  if (int rc = need_length(n)) return rc;
   if (B == 0) return ZMPC_OK;
   DeviceGuard g(P->device);
   if (g.err != hipSuccess) return hip_fail(g.err, "hipSetDevice");
@@ -787,9 +815,9 @@ int zmpc_herdt_prepare(const zmpc_plan* P, int64_t B, int64_t n, const int8_t* s
                        int32_t* nb_next, int32_t* max_steps, int32_t* max_footsteps_host) {
   g_err.clear();
   if (!P) return fail(ZMPC_EINVAL, "NULL plan");
-  if (B < 0 || n < 1) return fail(ZMPC_EINVAL, "need B >= 0 and n >= 1");
-  if (n > (1 << 24)) return fail(ZMPC_EINVAL, "walk too long");
-  if (B > 0x7fffffff) return fail(ZMPC_EINVAL, "batch too large");
+  if (int rc = need_walks(B, n)) return rc;
+  if (int rc = need_length(n)) return rc;
+  if (int rc = need_batch(B)) return rc;
   if (B > 0 && (!states || !nb_next)) return fail(ZMPC_EINVAL, "NULL array argument");
   if (s_stride != 0 && s_stride < n)
     return fail(ZMPC_EINVAL, "s_stride must be 0 (shared) or >= n");
@@ -828,7 +856,7 @@ int zmpc_herdt_step(const zmpc_plan* P, const zmpc_herdt_params* prm, int64_t B,
   if (B == 0) return ZMPC_OK;
   if (!x || !v_win || !s_win || !current || !foot || !side || !x_next || !step)
     return fail(ZMPC_EINVAL, "NULL array argument");
-  if (B > 0x7fffffff) return fail(ZMPC_EINVAL, "batch too large");
+  if (int rc = need_batch(B)) return rc;
   DeviceGuard g(P->device);
   if (g.err != hipSuccess) return hip_fail(g.err, "hipSetDevice");
   std::string why;

@@ -268,7 +268,7 @@ hipError_t zmpc_launch_trace_response(const zmpc_plan* p, const RolloutCall& c, 
                                       hipStream_t s);
 
 // The arguments of one zmpc_trace_margin call: B walks with `draws` rows each; push is the trace
-// of the B·draws rows in trace form (trace_args), L its samples per row as the caller gave them.
+// of the B·draws rows in trace form (capi.hip), L its samples per row as the caller gave them.
 struct MarginCall {
   int64_t B, n;
   const double *hist, *zmax, *zmin;

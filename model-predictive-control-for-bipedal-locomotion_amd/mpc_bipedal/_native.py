@@ -197,24 +197,19 @@ def check(rc: int, what: str):
         raise NativeError(f"{what} failed ({rc}): {msg}")
 
 
-def call_traced(name, device, trace, *args, raises=True):
-    """One launch of a symbol that takes its stream in a ZmpcTrace among its arguments: enter
-    HIP device `device`, put torch's current stream there into `trace` and call name(*args)."""
-    with torch.cuda.device(device):
-        trace.stream = torch.cuda.current_stream(device).cuda_stream
-        rc = getattr(load(), name)(*args)
-    if raises:
-        check(rc, name)
-    return rc
-
-
-def call(name, device, *args, after=(), raises=True):
+def call(name, device, *args, after=(), raises=True, trace=None):
     """One launch of a library symbol that takes a stream: enter HIP device `device`, call
     name(*args, torch's current stream there, *after) and run check on the result.
-    raises=False hands the return code back unchecked."""
+    raises=False hands the return code back unchecked.  trace: the ZmpcTrace among args of a
+    symbol that takes its stream there; the stream is put into it and no stream argument is
+    passed."""
     with torch.cuda.device(device):
         stream = torch.cuda.current_stream(device).cuda_stream
-        rc = getattr(load(), name)(*args, ctypes.c_void_p(stream), *after)
+        if trace is None:
+            args += (ctypes.c_void_p(stream),)
+        else:
+            trace.stream = stream
+        rc = getattr(load(), name)(*args, *after)
     if raises:
         check(rc, name)
     return rc

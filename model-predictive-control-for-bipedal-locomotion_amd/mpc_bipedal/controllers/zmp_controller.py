@@ -97,6 +97,45 @@ def _direction_size(direction, unit):
     return unit[:, 0] if unit.shape[0] > 1 else None
 
 
+def _batch_size(per_walk, sized, message):
+    """B of a scenario batch: the rows of the first argument of `per_walk` — (argument, its rank
+    when it holds one row per walk, None: whenever given) — that is per walk, else of the first
+    [B] argument of `sized` (the arguments that may be scalars or [B]), else 1.  A [B'] argument
+    of `sized` with B' != B raises ValueError(message.format(B=B))."""
+    named = [int(np.shape(a)[0]) for a, rank in per_walk
+             if a is not None and rank in (None, np.ndim(a))]
+    sizes = [int(np.shape(a)[0]) for a in sized if a is not None and np.ndim(a) == 1]
+    B = (named + sizes + [1])[0]
+    if any(s != B for s in sizes):
+        raise ValueError(message.format(B=B))
+    return B
+
+
+def _one_disturbance(F_ext, push, trace, force_step=None, walk_lengths=None):
+    """The batch methods take F_ext, a push or a trace, one of them; a push and a trace carry their
+    own start steps, so beside force_step or walk_lengths (where the method has them) they raise
+    too."""
+    if push is not None and F_ext is not None:
+        raise ValueError("give either F_ext or push, not both")
+    if trace is not None and (push is not None or F_ext is not None):
+        raise ValueError("give either trace or F_ext or push, not both")
+    for what, given in (("trace", trace), ("push", push)):
+        if given is not None and (force_step is not None or walk_lengths is not None):
+            raise ValueError(f"a {what} carries its own start step(s): force_step and "
+                             "walk_lengths belong to F_ext")
+
+
+def _trace_alone(trace, force_step, direction, D, w):
+    """A trace in a critical-force search stands for force_step, direction, duration and profile
+    (D, w: check_profile's answer): beside any of them it raises ValueError."""
+    if not isinstance(trace, PushTrace):
+        raise ValueError(f"trace must be an analysis.PushTrace, got {type(trace).__name__}")
+    if force_step is not None or np.ndim(direction) != 0 or direction != +1 or D != 1 \
+            or w is not None:
+        raise ValueError("a trace carries its own start steps, directions and shape: "
+                         "force_step, direction, duration and profile belong to a push")
+
+
 class ZMPController:
     """ZMP Controller using Model Predictive Control for bipedal locomotion."""
 
@@ -279,10 +318,7 @@ class ZMPController:
                 are unspecified but finite.
         trace : an analysis.PushTrace — a disturbance per walk, sample and axis instead of F_ext or
                 push (zmpc_herdt_rollout_traced; together with either it raises ValueError)."""
-        if push is not None and F_ext is not None:
-            raise ValueError("give either F_ext or push, not both")
-        if trace is not None and (push is not None or F_ext is not None):
-            raise ValueError("give either trace or F_ext or push, not both")
+        _one_disturbance(F_ext, push, trace)
         v = torch.as_tensor(v_ref, dtype=torch.float64)
         n = int(v.shape[-2])
         st = self._herdt_codes(state_ref)
@@ -396,26 +432,15 @@ class ZMPController:
                 F_ext, push, force_step or walk_lengths it raises ValueError
         Returns (hist [B,n,2,3], status [B]) on the plan's device.
         """
-        if push is not None and F_ext is not None:
-            raise ValueError("give either F_ext or push, not both")
-        if trace is not None and (push is not None or F_ext is not None):
-            raise ValueError("give either trace or F_ext or push, not both")
-        if trace is not None and (force_step is not None or walk_lengths is not None):
-            raise ValueError("a trace carries its own start step(s): force_step and walk_lengths "
-                             "belong to F_ext")
-        if push is not None and (force_step is not None or walk_lengths is not None):
-            raise ValueError("a push carries its own start step(s): force_step and walk_lengths "
-                             "belong to F_ext")
+        _one_disturbance(F_ext, push, trace, force_step, walk_lengths)
         plan, zmax_t, zmin_t, x0, kick, step = self._batch_inputs(x_init, z_max, z_min, F_ext,
                                                                   force_step, walk_lengths)
-        if push is not None:
-            if x_init is None and zmax_t.dim() == 2 and push.batch():
-                x0 = x0.expand(push.batch(), 2, 3).contiguous()
-            hist, st = plan.rollout(zmax_t, zmin_t, x0, push=push, mass=self.config.m)
-        elif trace is not None:
-            if x_init is None and zmax_t.dim() == 2:
-                x0 = x0.expand(trace.batch(), 2, 3).contiguous()
-            hist, st = plan.rollout(zmax_t, zmin_t, x0, trace=trace, mass=self.config.m)
+        given = push if push is not None else trace
+        if given is not None:
+            if x_init is None and zmax_t.dim() == 2 and given.batch():
+                x0 = x0.expand(given.batch(), 2, 3).contiguous()
+            hist, st = plan.rollout(zmax_t, zmin_t, x0, push=push, trace=trace,
+                                    mass=self.config.m)
         else:
             hist, st = plan.rollout(zmax_t, zmin_t, x0, kick=kick, kick_step=step)
         if plan.strict:
@@ -431,17 +456,10 @@ class ZMPController:
         f64 = dict(dtype=torch.float64, device=torch.device("cuda", plan.device))
         zmax_t = torch.as_tensor(z_max, **f64).contiguous()
         zmin_t = torch.as_tensor(z_min, **f64).contiguous()
-        sizes = [int(np.shape(a)[0]) for a in sized if a is not None and np.ndim(a) == 1]
-        if x_init is not None:
-            x0 = torch.as_tensor(x_init, **f64)
-            B = int(x0.shape[0])
-        else:
-            B = int(zmax_t.shape[0]) if zmax_t.dim() == 3 else (sizes[0] if sizes else 1)
-            x0 = torch.zeros((B, 2, 3), **f64)
-        if any(s != B for s in sizes):
-            raise ValueError("force_step, direction and walk_lengths must be scalars or "
-                             f"[B] = [{B}]"
-                             + (" (planar directions [1, 2] or [B, 2])" if planar else ""))
+        B = _batch_size(((x_init, None), (zmax_t, 3)), sized,
+                        "force_step, direction and walk_lengths must be scalars or [B] = [{B}]"
+                        + (" (planar directions [1, 2] or [B, 2])" if planar else ""))
+        x0 = torch.zeros((B, 2, 3), **f64) if x_init is None else torch.as_tensor(x_init, **f64)
         lengths = None
         if walk_lengths is not None:
             lengths = torch.as_tensor(walk_lengths, dtype=torch.int64,
@@ -564,12 +582,7 @@ class ZMPController:
         planar = np.ndim(direction) == 2
         traced = trace is not None
         if traced:
-            if not isinstance(trace, PushTrace):
-                raise ValueError(f"trace must be an analysis.PushTrace, got {type(trace).__name__}")
-            if force_step is not None or planar or D != 1 or w is not None or \
-                    not (np.ndim(direction) == 0 and direction == +1):
-                raise ValueError("a trace carries its own start steps, directions and shape: "
-                                 "force_step, direction, duration and profile belong to a push")
+            _trace_alone(trace, force_step, direction, D, w)
             if fused:
                 raise ValueError("fused=True has no traced form: a trace runs a traced rollout "
                                  "plus walk_metrics")
@@ -587,26 +600,25 @@ class ZMPController:
                    np.empty(trace.batch()) if traced else None), planar=True)
         if not (F_hi > 0) or iters < 0:
             raise ValueError("need F_hi > 0 and iters >= 0")
-        if planar:
-            sign = None
-        else:
-            sign = torch.sign(torch.as_tensor(direction, **f64)).expand(B).contiguous()
+        sign = None if planar else \
+            torch.sign(torch.as_tensor(direction, **f64)).expand(B).contiguous()
         step = _force_step(force_step, n, lengths)
         if not isinstance(step, int):
             step = torch.as_tensor(step, dtype=torch.int64, device=dev)
         kick = torch.zeros(B, **f64)
         metrics = torch.empty((B, NMETRICS), **f64)
+        scaled = unit1 = None  # a shove's or trace's buffer the launch reads, and its copy for 1 N
         if traced:
             # (a copy of the trace at scale 1: the launch's buffer is rewritten per evaluation)
             launch = plan.rollout_launcher(zmax_t, zmin_t, x0, trace=trace.scaled(1.0),
                                            mass=self.config.m)
-            dv1 = launch.trace_dv.clone()  # [B, L, C] at λ = 1
+            scaled, unit1 = launch.trace_dv, launch.trace_dv.clone()  # [B, L, C] at λ = 1
         elif shove:
             F1, d1 = _unit_push(None if planar else sign.cpu().numpy(), unit, B)
             st = step.cpu().numpy() if isinstance(step, torch.Tensor) else step
             push = Push(F1, d1, st, duration=D, profile=w)
             launch = plan.rollout_launcher(zmax_t, zmin_t, x0, push=push, mass=self.config.m)
-            amp1 = launch.push_amp.clone()  # [B, C] for 1 N
+            scaled, unit1 = launch.push_amp, launch.push_amp.clone()  # [B, C] for 1 N
         elif fused:
             launch = plan.rollout_metrics_launcher(zmax_t, zmin_t, x0, kick=kick, kick_step=step,
                                                    lengths=lengths, out=metrics)
@@ -616,10 +628,8 @@ class ZMPController:
         dt, mass = self.config.dt, self.config.m
 
         def passes(F):
-            if traced:
-                launch.trace_dv.copy_(dv1 * F[:, None, None])
-            elif shove:
-                launch.push_amp.copy_(amp1 * F[:, None])
+            if scaled is not None:
+                scaled.copy_(unit1 * F.reshape((-1,) + (1,) * (unit1.dim() - 1)))
             else:
                 kick.copy_(dt * (sign * F) / mass)  # zmp_controller.py:106
             launch()
@@ -704,12 +714,7 @@ class ZMPController:
         D, w = check_profile(duration, profile)
         traced = trace is not None
         if traced:
-            if not isinstance(trace, PushTrace):
-                raise ValueError(f"trace must be an analysis.PushTrace, got {type(trace).__name__}")
-            if force_step is not None or np.ndim(direction) != 0 or direction != +1 or D != 1 \
-                    or w is not None:
-                raise ValueError("a trace carries its own start steps, directions and shape: "
-                                 "force_step, direction, duration and profile belong to a push")
+            _trace_alone(trace, force_step, direction, D, w)
         if max_dcm_dev is None or not (float(max_dcm_dev) > 0):
             raise ValueError("max_dcm_dev must be a positive bound in metres: the ZMP of a Herdt "
                              "walk never tells whether the robot fell, the DCM does")
@@ -725,18 +730,9 @@ class ZMPController:
         st = self._herdt_codes(state_ref)
         sized = (force_step, _direction_size(direction, unit), walk_lengths,
                  np.empty(trace.batch()) if traced else None)
-        sizes = [int(np.shape(a)[0]) for a in sized if a is not None and np.ndim(a) == 1]
-        if x_init is not None:
-            B = int(np.shape(x_init)[0])
-        elif v.dim() == 3:
-            B = int(v.shape[0])
-        elif st.ndim == 2:
-            B = int(st.shape[0])
-        else:
-            B = sizes[0] if sizes else 1
-        if any(s != B for s in sizes):
-            raise ValueError(f"force_step and direction must be scalars or [B] = [{B}] (planar "
-                             "directions [1, 2] or [B, 2])")
+        B = _batch_size(((x_init, None), (v, 3), (st, 2)), sized,
+                        "force_step and direction must be scalars or [B] = [{B}] (planar "
+                        "directions [1, 2] or [B, 2])")
         x0 = torch.zeros((B, 2, 3), **f64) if x_init is None else torch.as_tensor(x_init, **f64)
         lengths = None
         if force_step is None and walk_lengths is not None:
@@ -848,7 +844,7 @@ class ZMPController:
                                      axes="xy" if planar else "y")
         if planar:
             return planar_push(force, limit, unit)[0]
-        sign =torch.as_tensor(direction, dtype=torch.float64, device=dev).expand(B)
+        sign = torch.as_tensor(direction, dtype=torch.float64, device=dev).expand(B)
         return torch.where(sign >= 0, force[:, 0], force[:, 1])
 
     def trace_margin(self, z_max, z_min, trace: PushTrace, x_init=None, walk_lengths=None,

@@ -24,16 +24,28 @@ _PLAN_CACHE = OrderedDict()
 _PLAN_CACHE_LOCK = threading.Lock()
 PLAN_CACHE_MAX = max(1, int(os.environ.get("ZMPC_PLAN_CACHE", "8")))
 
+
+class _Disturbance:
+    """What disturbs the walks of a rollout, as the C-ABI takes it (Plan._disturbance): the C
+    symbol's suffix ("", "_kicks", "_pushed" or "_traced"), the C arguments between x0 and the
+    outputs, what they point to (keep: the kick tensors; else the struct and the tensors it points
+    to), the device tensor a caller may rescale between launches (scaled: the kick [B], the
+    amplitudes [B, C] or the velocity steps [B, L, C]; None without a kick) and the
+    _native.ZmpcTrace whose `stream` field takes the stream (trace; None for the symbols that
+    take a stream argument)."""
+    __slots__ = ("suffix", "args", "keep", "scaled", "trace")
+
+    def __init__(self, suffix, args, keep, scaled, trace=None):
+        self.suffix, self.args, self.keep, self.scaled, self.trace = (suffix, args, keep, scaled,
+                                                                      trace)
+
+    def attrs(self):
+        """What a rollout launcher exposes of it: push_amp on every form, trace_dv if traced."""
+        amp = self.scaled if self.suffix == "_pushed" else None
+        return dict(push_amp=amp, **({} if self.trace is None else {"trace_dv": self.scaled}))
+
+
 # what Plan._out raises for a state history and for a metrics tensor
-class _Traced:
-    """What a traced launch reads: the _native.ZmpcTrace (it carries the stream) and the device
-    tensors it points to, dv [B, L, C] and the start steps [B] or None."""
-    __slots__ = ("struct", "dv", "steps")
-
-    def __init__(self, struct, dv, steps):
-        self.struct, self.dv, self.steps = struct, dv, steps
-
-
 _HIST_MSG = "hist must be a contiguous float64 [B, n, 2, 3] tensor on the plan's device"
 _METRICS_MSG = (f"out must be a contiguous float64 [B, {_native.NMETRICS}] tensor on the plan's "
                 "device")
@@ -53,6 +65,15 @@ def _device_index(backend: str) -> int:
 
 def _ptr(t):
     return ctypes.c_void_p(t.data_ptr()) if t is not None else None
+
+
+def _ints(a, dtype, device):
+    """Support states (np.int8) or step counts (np.int32) as a contiguous tensor of that type on
+    the device; a tensor is converted where it is, never through the host."""
+    if not isinstance(a, torch.Tensor):
+        a = np.asarray(a, dtype=dtype)
+    return torch.as_tensor(a, dtype=getattr(torch, np.dtype(dtype).name),
+                           device=device).contiguous()
 
 
 class Plan:
@@ -214,62 +235,59 @@ class Plan:
             return kick_t, int(kick_step), None
         return kick_t, -1, self._index(kick_step, B, "per-walk kick_step", sized=False)
 
-    def _push_struct(self, push, mass, B, kick=None):
-        """An analysis.Push as the C-ABI takes it: (_native.ZmpcPush, the device tensors it points
-        to).  The amplitudes need the robot's mass (the plan holds dt, not m).  kick: the
-        caller's one-sample kick, which a push excludes."""
-        from .analysis import AXES, Push
+    def _disturbance(self, kick, kick_step, push, trace, mass, B, kicks=True):
+        """The one disturbance of B walks as the C-ABI takes it → _Disturbance: the one-sample y
+        kick (kick [B] or None at kick_step; kicks=False for a call without that form), an
+        analysis.Push or an analysis.PushTrace, each of which excludes the others.  Amplitudes and
+        a trace in newtons need the robot's mass (the plan holds dt, not m); velocity steps on the
+        plan's device are used as they are, without a copy."""
+        from .analysis import AXES, Push, PushTrace
+        if kicks and push is None and trace is None:
+            kick_t, step, ks = self._kick(kick, kick_step, B)
+            if ks is None:
+                return _Disturbance("", (_ptr(kick_t), step), (kick_t,), kick_t)
+            return _Disturbance("_kicks", (_ptr(kick_t), _ptr(ks)), (kick_t, ks), kick_t)
+        if trace is not None and (kick is not None or push is not None):
+            raise ValueError("give either trace or a kick or push, not both")
         if kick is not None:
             raise ValueError("give either kick or push, not both")
-        if not isinstance(push, Push):
-            raise ValueError(f"push must be an analysis.Push, got {type(push).__name__}")
-        if mass is None or not (float(mass) > 0) or not np.isfinite(float(mass)):
-            raise ValueError("a push needs the robot's mass in kg (mass=), finite and positive")
+        what, kind, src = ("push", Push, push) if push is not None else ("trace", PushTrace, trace)
+        if not isinstance(src, kind):
+            raise ValueError(f"{what} must be an analysis.{kind.__name__}, got "
+                             f"{type(src).__name__}")
+        newtons = push is not None or trace.unit != "m/s"
+        if newtons and (mass is None or not (float(mass) > 0) or not np.isfinite(float(mass))):
+            raise ValueError("a push needs the robot's mass in kg (mass=), finite and positive"
+                             if push is not None else "a trace in newtons needs the robot's mass "
+                             "in kg (mass=), finite and positive")
         dev = self._device
+
+        def start():  # the start step(s) as (scalar, [B] tensor): one of the two holds them
+            if isinstance(src.step, int):
+                return src.step, None
+            return -1, torch.as_tensor(np.broadcast_to(src.step, (B,)).copy(), device=dev)
+        # (the arguments hold the struct's address: it lives in what the caller keeps)
+        if push is None:
+            dv = trace.dv(self.dt, None if mass is None else float(mass), B)
+            dv = torch.as_tensor(dv, dtype=torch.float64, device=dev).contiguous()
+            step, steps = start()
+            c = _native.ZmpcTrace(dv.data_ptr(), AXES[trace.axes], _ptr(steps), step,
+                                  trace.length, None)
+            return _Disturbance("_traced", (ctypes.addressof(c),), (c, (dv, steps)), dv, c)
         amp = torch.as_tensor(push.amplitudes(self.dt, float(mass), B), device=dev)
         prof = None if push.profile is None else torch.as_tensor(push.profile, device=dev)
-        if isinstance(push.step, int):
-            step, steps = push.step, None
-        else:
-            step = -1
-            steps = torch.as_tensor(np.broadcast_to(push.step, (B,)).copy(), device=dev)
-        c = _native.ZmpcPush(amp.data_ptr(), AXES[push.axes],
-                             None if steps is None else steps.data_ptr(), step,
-                             None if prof is None else prof.data_ptr(), push.duration)
-        return c, (amp, steps, prof)
-
-    def _trace_struct(self, trace, mass, B, kick=None, push=None):
-        """An analysis.PushTrace as the C-ABI takes it: a _Traced (the _native.ZmpcTrace and the
-        device tensors it points to).  A trace in newtons needs the robot's mass; velocity
-        steps on the plan's device are used as they are, without a copy.  kick, push: the
-        caller's other disturbances, which a trace excludes."""
-        from .analysis import AXES, PushTrace
-        if kick is not None or push is not None:
-            raise ValueError("give either trace or a kick or push, not both")
-        if not isinstance(trace, PushTrace):
-            raise ValueError(f"trace must be an analysis.PushTrace, got {type(trace).__name__}")
-        if trace.unit != "m/s" and (mass is None or not (float(mass) > 0)
-                                    or not np.isfinite(float(mass))):
-            raise ValueError("a trace in newtons needs the robot's mass in kg (mass=), finite and "
-                             "positive")
-        dev = self._device
-        dv = trace.dv(self.dt, None if mass is None else float(mass), B)
-        dv = torch.as_tensor(dv, dtype=torch.float64, device=dev).contiguous()
-        if isinstance(trace.step, int):
-            step, steps = trace.step, None
-        else:
-            step = -1
-            steps = torch.as_tensor(np.broadcast_to(trace.step, (B,)).copy(), device=dev)
-        c = _native.ZmpcTrace(dv.data_ptr(), AXES[trace.axes],
-                              None if steps is None else steps.data_ptr(), step, trace.length,
-                              None)
-        return _Traced(c, dv, steps)
+        step, steps = start()
+        c = _native.ZmpcPush(amp.data_ptr(), AXES[push.axes], _ptr(steps), step, _ptr(prof),
+                             push.duration)
+        return _Disturbance("_pushed", (ctypes.addressof(c),), (c, (amp, steps, prof)), amp)
 
     # -- launches --------------------------------------------------------------------------
-    def _launcher(self, name, args, **attrs):
+    def _launcher(self, name, args, trace=None, **attrs):
         """A zero-argument callable that re-issues name(*args, current stream) and carries
         attrs.  One launch is one stream lookup and one ctypes call: no device context, no
-        argument work, and _native.check only on a nonzero return."""
+        argument work, and _native.check only on a nonzero return.  trace: the ZmpcTrace among
+        args of a call that takes its stream there — one launch is then one stream lookup, one
+        store into the struct and one ctypes call."""
         fn = getattr(_native.load(), name)
         dev = self.device
 
@@ -278,20 +296,14 @@ class Plan:
             rc = fn(*args, ctypes.c_void_p(stream))
             if rc != 0:
                 _native.check(rc, name)
-        launch.__dict__.update(attrs)
-        return launch
 
-    def _launcher_traced(self, name, args, c, **attrs):
-        """_launcher for the calls that take their stream in a ZmpcTrace `c` among args: one
-        launch is one stream lookup, one store into the struct and one ctypes call."""
-        fn = getattr(_native.load(), name)
-        dev = self.device
-
-        def launch():
-            c.stream = torch.cuda.current_stream(dev).cuda_stream
+        def launch_traced():
+            trace.stream = torch.cuda.current_stream(dev).cuda_stream
             rc = fn(*args)
             if rc != 0:
                 _native.check(rc, name)
+        if trace is not None:
+            launch = launch_traced
         launch.__dict__.update(attrs)
         return launch
 
@@ -318,14 +330,12 @@ class Plan:
         new amplitudes into it between launches, as critical_force does).  trace: an
         analysis.PushTrace instead; launch.trace_dv is then the [B, L, C] tensor of velocity steps
         the launch reads."""
-        hist, status, (name, args, keep) = self._rollout_args(zmax, zmin, x0, kick, kick_step,
-                                                              hist, status, push, mass, trace)
-        if trace is not None:
-            traced = keep[-1]
-            return self._launcher_traced(name, args, traced.struct, hist=hist, status=status,
-                                         inputs=keep, push_amp=None, trace_dv=traced.dv)
-        return self._launcher(name, args, hist=hist, status=status, inputs=keep,
-                              push_amp=keep[-1][0] if push is not None else None)
+        hist, status, name, args, walks, d = self._rollout_args(zmax, zmin, x0, kick, kick_step,
+                                                                hist, status, push, mass, trace)
+        # (inputs: the walks, then what the disturbance's arguments point to; a traced launch
+        # shows the _Disturbance itself, one entry)
+        return self._launcher(name, args, d.trace, hist=hist, status=status,
+                              inputs=walks + (d.keep if d.trace is None else (d,)), **d.attrs())
 
     def rollout(self, zmax, zmin, x0, kick=None, kick_step=-1, hist=None, status=None,
                 push=None, mass=None, trace=None):
@@ -335,12 +345,9 @@ class Plan:
         in kg, needed with push.  trace: an analysis.PushTrace — a disturbance per walk, sample
         and axis (zmpc_rollout_traced; not together with kick or push); mass is needed when the
         trace is in newtons."""
-        hist, status, (name, args, keep) = self._rollout_args(zmax, zmin, x0, kick, kick_step,
-                                                              hist, status, push, mass, trace)
-        if trace is not None:
-            _native.call_traced(name, self.device, keep[-1].struct, *args)
-        else:
-            _native.call(name, self.device, *args)
+        hist, status, name, args, _, d = self._rollout_args(zmax, zmin, x0, kick, kick_step, hist,
+                                                            status, push, mass, trace)
+        _native.call(name, self.device, *args, trace=d.trace)
         return hist, status
 
     def _walk_inputs(self, zmax, zmin, x0):
@@ -356,32 +363,17 @@ class Plan:
         zmax/zmin: [B,n,2] per-walk CoP bounds, or [n,2] one CoP shared by every walk;
         x0: [B,2,3]; kick: [B] velocity impulse subtracted from y at step kick_step — an int,
         or a [B] array of per-walk steps (ragged walks: zmpc_rollout_kicks).
-        Returns (hist, status, (symbol, its arguments without the stream, what they point to)).
+        Returns (hist, status, symbol, its arguments without the stream, the walks' tensors, the
+        _Disturbance: a traced symbol takes the stream in its struct, no stream argument follows).
         """
         zmax, zmin, x0, B, n, bstride = self._walk_inputs(zmax, zmin, x0)
         hist = self._out(hist, (B, n, 2, 3), torch.float64, _HIST_MSG)
         if status is None:
             status = torch.empty(B, dtype=torch.int32, device=self._device)
-        walks = (self._live(), B, n, _ptr(zmax), _ptr(zmin), bstride, _ptr(x0))
-        outs = (_ptr(hist), _ptr(status))
-        if trace is not None:
-            traced = self._trace_struct(trace, mass, B, kick, push)
-            # (the struct carries the stream: no stream argument follows; what the arguments
-            # point to ends with the _Traced, by which the callers name the struct and dv)
-            return hist, status, ("zmpc_rollout_traced",
-                                  walks + (ctypes.addressof(traced.struct),) + outs,
-                                  (zmax, zmin, x0, traced))
-        if push is not None:
-            c, keep = self._push_struct(push, mass, B, kick)
-            # (the arguments hold the struct's address: it lives in what the launcher keeps)
-            return hist, status, ("zmpc_rollout_pushed", walks + (ctypes.addressof(c),) + outs,
-                                  (zmax, zmin, x0, c, keep))
-        kick_t, step, ks = self._kick(kick, kick_step, B)
-        if ks is None:
-            return hist, status, ("zmpc_rollout", walks + (_ptr(kick_t), step) + outs,
-                                  (zmax, zmin, x0, kick_t))
-        return hist, status, ("zmpc_rollout_kicks", walks + (_ptr(kick_t), _ptr(ks)) + outs,
-                              (zmax, zmin, x0, kick_t, ks))
+        d = self._disturbance(kick, kick_step, push, trace, mass, B)
+        args = (self._live(), B, n, _ptr(zmax), _ptr(zmin), bstride, _ptr(x0), *d.args,
+                _ptr(hist), _ptr(status))
+        return hist, status, "zmpc_rollout" + d.suffix, args, (zmax, zmin, x0), d
 
     def walk_metrics(self, hist, zmax, zmin, lengths=None, out=None):
         """Per-walk robustness metrics of a state history (zmpc_walk_metrics, include/zmpc.h)
@@ -482,15 +474,14 @@ class Plan:
         if isinstance(trace, PushTrace) and trace.batch() != B * K:
             raise ValueError(f"the trace holds {trace.batch()} rows, B·draws = {B}·{K} = {B * K} "
                              "are needed (row b·draws + k is draw k of walk b)")
-        traced = self._trace_struct(trace, mass, B * K)
+        d = self._disturbance(None, -1, None, trace, mass, B * K, kicks=False)
         msg = (f"scale and limit must be (float64, int32) contiguous {(B, K, 2)} tensors on the "
                "plan's device")
         scale = self._out(scale, (B, K, 2), torch.float64, msg)
         limit = self._out(limit, (B, K, 2), torch.int32, msg)
-        _native.call_traced("zmpc_trace_margin", self.device, traced.struct, self._live(), B, n,
-                            _ptr(hist), _ptr(zmax), _ptr(zmin), bstride, _ptr(len_t), K,
-                            ctypes.addressof(traced.struct), float(max_violation), _ptr(scale),
-                            _ptr(limit))
+        _native.call("zmpc_trace_margin", self.device, self._live(), B, n, _ptr(hist), _ptr(zmax),
+                     _ptr(zmin), bstride, _ptr(len_t), K, *d.args, float(max_violation),
+                     _ptr(scale), _ptr(limit), trace=d.trace)
         return scale, limit
 
     # -- fused rollout-to-metrics (zmpc_rollout_metrics) -----------------------------------
@@ -542,9 +533,9 @@ class Plan:
     # -- Herdt joint footstep QP (zmpc_herdt_rollout / zmpc_herdt_step) --------------------
     def _herdt_rollout_args(self, params, v_ref, states, nb_next, x0, kick, kick_step, push, mass,
                             hist=None, foot=None, status=None, trace=None):
-        """The checked arguments of one Herdt rollout → (hist, foot, status, (symbol, its
-        arguments without the stream, what they point to)); hist, foot, status: tensors to write
-        into, or None for new ones."""
+        """The checked arguments of one Herdt rollout → (hist, foot, status, symbol, its arguments
+        without the stream, the walks' tensors, the _Disturbance); hist, foot, status: tensors to
+        write into, or None for new ones."""
         x0, B = self._x0(x0)
         v = self._as_dev(v_ref)
         if v.dim() not in (2, 3) or v.shape[-1] != 2:
@@ -559,9 +550,7 @@ class Plan:
         # per-walk [B, n] or shared [n]: a 2-D array must carry one row per walk (the kernel
         # reads row b of walk b)
         st, ss = self._states(states, B, n)
-        nb = torch.as_tensor(np.asarray(nb_next, dtype=np.int32) if not isinstance(
-            nb_next, torch.Tensor) else nb_next, dtype=torch.int32,
-            device=self._device).contiguous()
+        nb = _ints(nb_next, np.int32, self._device)
         if tuple(nb.shape) not in ((n,), (B, n)):
             raise ValueError(f"nb_next must be [B, n] = [{B}, {n}] or [n], got {tuple(nb.shape)}")
         ns = 0 if nb.dim() == 1 else n
@@ -571,20 +560,12 @@ class Plan:
                          "foot must be a contiguous float64 [B, n, 2] tensor on the plan's device")
         status = self._out(status, (B,), torch.int32,
                            "status must be a contiguous int32 [B] tensor on the plan's device")
-        if trace is not None:
-            keep = self._trace_struct(trace, mass, B, kick, push)  # (a _Traced, named below)
-            c = keep.struct
-            name, disturbance = "zmpc_herdt_rollout_traced", (ctypes.addressof(c),)
-        elif push is not None:
-            c, keep = self._push_struct(push, mass, B, kick)
-            # (the arguments hold the struct's address: it lives in what the caller keeps)
-            name, disturbance = "zmpc_herdt_rollout_pushed", (ctypes.addressof(c),)
-        else:
-            c, keep = None, ()
-            name, disturbance = "zmpc_herdt_rollout", (_ptr(kick_t), int(kick_step))
+        step = int(kick_step) if push is None and trace is None else -1  # (no per-walk form)
+        d = self._disturbance(kick_t, step, push, trace, mass, B)
         args = (self._live(), ctypes.addressof(params), B, n, _ptr(v), vs, _ptr(st), ss, _ptr(nb),
-                ns, _ptr(x0), *disturbance, _ptr(hist), _ptr(foot), _ptr(status))
-        return hist, foot, status, (name, args, (params, v, st, nb, x0, kick_t, c, keep))
+                ns, _ptr(x0), *d.args, _ptr(hist), _ptr(foot), _ptr(status))
+        return (hist, foot, status, "zmpc_herdt_rollout" + d.suffix, args,
+                (params, v, st, nb, x0, kick_t), d)
 
     def herdt_rollout(self, params, v_ref, states, nb_next, x0, kick=None, kick_step=-1,
                       push=None, mass=None, trace=None):
@@ -596,12 +577,9 @@ class Plan:
         push: an analysis.Push instead of the kick (zmpc_herdt_rollout_pushed), with mass in kg.
         trace: an analysis.PushTrace instead of either (zmpc_herdt_rollout_traced).
         """
-        hist, foot, status, (name, args, keep) = self._herdt_rollout_args(
+        hist, foot, status, name, args, _, d = self._herdt_rollout_args(
             params, v_ref, states, nb_next, x0, kick, kick_step, push, mass, trace=trace)
-        if trace is not None:
-            _native.call_traced(name, self.device, keep[-1].struct, *args)
-        else:
-            _native.call(name, self.device, *args)
+        _native.call(name, self.device, *args, trace=d.trace)
         return hist, foot, status
 
     def herdt_rollout_launcher(self, params, v_ref, states, nb_next, x0, push=None, mass=None,
@@ -613,21 +591,19 @@ class Plan:
         amplitudes into it between launches, as critical_force_herdt does).  trace: an
         analysis.PushTrace instead of push (zmpc_herdt_rollout_traced); launch.trace_dv is then
         the [B, L, C] tensor of velocity steps the launch reads."""
-        hist, foot, status, (name, args, keep) = self._herdt_rollout_args(
+        hist, foot, status, name, args, walks, d = self._herdt_rollout_args(
             params, v_ref, states, nb_next, x0, None, -1, push, mass, hist, foot, status, trace)
-        if trace is not None:
-            traced = keep[-1]
-            return self._launcher_traced(name, args, traced.struct, hist=hist, foot=foot,
-                                         status=status, inputs=keep, states=keep[2],
-                                         push_amp=None, trace_dv=traced.dv)
-        return self._launcher(name, args, hist=hist, foot=foot, status=status, inputs=keep,
-                              states=keep[2], push_amp=keep[-1][0])
+        _, _, st, *_ = walks
+        # (inputs: the walks, the struct, then the tensors it points to; a traced launch shows
+        # the _Disturbance itself there)
+        return self._launcher(name, args, d.trace, hist=hist, foot=foot, status=status,
+                              inputs=walks + (d.keep if d.trace is None else (d.trace, d)),
+                              states=st, **d.attrs())
 
     def _states(self, states, B, n):
         """Support states on the device → (int8 tensor, stride in bytes between walks): [B, n]
         per walk (stride n) or a shared [n] (stride 0)."""
-        st = torch.as_tensor(np.asarray(states, dtype=np.int8) if not isinstance(
-            states, torch.Tensor) else states, dtype=torch.int8, device=self._device).contiguous()
+        st = _ints(states, np.int8, self._device)
         if tuple(st.shape) not in ((n,), (B, n)):
             raise ValueError(f"states must be [B, n] = [{B}, {n}] or [n], got {tuple(st.shape)}")
         return st, (0 if st.dim() == 1 else n)
@@ -644,8 +620,7 @@ class Plan:
         whatever rows n_b.. of the input hold.  A shared [n] input without lengths gives [n], [n]
         and [1]; with lengths [B] it is one schedule cut at B lengths.  Synchronous: the call
         waits for the device on entry and returns with every output complete."""
-        st = torch.as_tensor(np.asarray(states, dtype=np.int8) if not isinstance(
-            states, torch.Tensor) else states, dtype=torch.int8, device=self._device).contiguous()
+        st = _ints(states, np.int8, self._device)
         if st.dim() not in (1, 2) or st.shape[-1] < 1:
             raise ValueError(f"states must be [B, n] or [n] with n >= 1, got {tuple(st.shape)}")
         n = int(st.shape[-1])
@@ -731,9 +706,8 @@ class Plan:
         dev = self._device
         v = self._as_dev(v_win, (B, self.N, 2))
         f = self._as_dev(foot, (B, 2))
-        i8 = lambda a, shape: torch.as_tensor(np.asarray(a, dtype=np.int8).reshape(shape),
-                                              device=dev).contiguous()
-        sw, cu, sd = i8(s_win, (B, self.N)), i8(current, (B,)), i8(side, (B,))
+        sw, cu, sd = (_ints(a, np.int8, dev).reshape(shape)
+                      for a, shape in ((s_win, (B, self.N)), (current, (B,)), (side, (B,))))
         xn = torch.empty((B, 2, 3), dtype=torch.float64, device=dev)
         step = torch.empty((B, 2), dtype=torch.float64, device=dev)
         status = torch.empty(B, dtype=torch.int32, device=dev)

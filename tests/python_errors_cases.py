@@ -5,14 +5,16 @@ smallest shapes — unconstrained and strict plans at N = 8, B = 2 walks of n = 
 Each row is (id, callable of the shared context).  What a row must raise — the exception type
 and str(exc), character for character — was recorded from the commit before the checked-argument
 layer (tests/golden/make_python_errors_golden.py → tests/golden/python_errors.json), and so was
-what the launchers keep alive (LAUNCHERS, describe).  Needs a HIP device: the checks build
-device tensors.
+what the launchers keep alive (LAUNCHERS, describe).  The rows that involve a trace, the sizing of
+critical_force_herdt and the Herdt and traced launchers were recorded the same way from the commit
+before the disturbances' host side was merged into one path.  Needs a HIP device: the checks
+build device tensors.
 """
 import numpy as np
 import torch
 
 from mpc_bipedal import _native
-from mpc_bipedal.analysis import Push
+from mpc_bipedal.analysis import Push, PushTrace
 from mpc_bipedal.config import MPCConfig
 from mpc_bipedal.controllers import ZMPController, herdt
 from mpc_bipedal.generators.cop_generator import generate_cop_batch
@@ -44,6 +46,13 @@ class Context:
         self.v = np.zeros((B, n, 2))
         self.st = np.zeros((B, n), np.int8)
         self.nb = np.ones((B, n), np.int32)
+        self.trace = PushTrace(np.ones((B, 2)), 1)  # newtons on y: it needs the mass
+        # ... and one short gait whose launchers are issued (launchers)
+        hs = np.array([herdt.STANDING] * 2 + ([herdt.DOUBLE_SUPPORT] * 2
+                                              + [herdt.SINGLE_SUPPORT] * 4) * 2, np.int8)
+        self.hst, self.hnb, _, most = self.up.herdt_prepare(np.stack([hs, hs]))
+        self.hprm = herdt.make_params(self.ch.config, most)
+        self.hv = np.tile([0.1, 0.0], (B, len(hs), 1))
 
     def t(self, *shape, dtype=torch.float64):
         return torch.zeros(shape, dtype=dtype, device=self.dev)
@@ -120,6 +129,25 @@ def rows():
             lambda c, p=plan: p(c).rollout_launcher(c.zmax, c.zmin, c.x0, kick=np.zeros(B),
                                                     push=c.push, mass=MASS))
 
+        # ... and a trace beside or instead of them
+        roll = lambda c, p=plan, **kw: p(c).rollout(c.zmax, c.zmin, c.x0, **kw)  # noqa: E731
+        add(f"rollout/{tag}/trace_and_kick",
+            lambda c, roll=roll: roll(c, kick=np.zeros(B), trace=c.trace, mass=MASS))
+        add(f"rollout/{tag}/trace_and_push",
+            lambda c, roll=roll: roll(c, push=c.push, trace=c.trace, mass=MASS))
+        add(f"rollout/{tag}/trace_type", lambda c, roll=roll: roll(c, trace=c.push, mass=MASS))
+        for mtag, mass in (("none", None), ("zero", 0.0), ("inf", float("inf"))):
+            add(f"rollout/{tag}/trace_mass_{mtag}",
+                lambda c, roll=roll, mass=mass: roll(c, trace=c.trace, mass=mass))
+        add(f"rollout/{tag}/trace_batch",
+            lambda c, roll=roll: roll(c, trace=PushTrace(np.ones((3, 2)), 1), mass=MASS))
+        add(f"launcher/{tag}/trace_and_kick",
+            lambda c, p=plan: p(c).rollout_launcher(c.zmax, c.zmin, c.x0, kick=np.zeros(B),
+                                                    trace=c.trace, mass=MASS))
+        add(f"launcher/{tag}/trace_and_push",
+            lambda c, p=plan: p(c).rollout_launcher(c.zmax, c.zmin, c.x0, push=c.push,
+                                                    trace=c.trace, mass=MASS))
+
     # Plan.walk_metrics and Plan.push_map share the history, bounds and lengths rules
     calls = (("walk_metrics", lambda c, h, hi, lo, **kw: c.up.walk_metrics(h, hi, lo, **kw)),
              ("push_map", lambda c, h, hi, lo, **kw: c.up.push_map(h, hi, lo, mass=MASS, **kw)))
@@ -191,7 +219,113 @@ def rows():
     add("herdt_rollout/push_type", lambda c: hr(c, push=(10.0, 1), mass=MASS))
     add("herdt_rollout/mass_none", lambda c: hr(c, push=c.push))
 
+    add("herdt_rollout/trace_and_kick",
+        lambda c: hr(c, kick=np.zeros(B), trace=c.trace, mass=MASS))
+    add("herdt_rollout/trace_and_push", lambda c: hr(c, push=c.push, trace=c.trace, mass=MASS))
+    add("herdt_rollout/trace_type", lambda c: hr(c, trace=[[1.0]], mass=MASS))
+    add("herdt_rollout/trace_mass_none", lambda c: hr(c, trace=c.trace))
+    add("herdt_rollout/trace_batch",
+        lambda c: hr(c, trace=PushTrace(np.ones((3, 2)), 1), mass=MASS))
+    hl = lambda c, **kw: c.up.herdt_rollout_launcher(  # noqa: E731
+        c.prm, c.v, c.st, c.nb, c.x0, **kw)
+    add("herdt_rollout_launcher/trace_and_push",
+        lambda c: hl(c, push=c.push, trace=c.trace, mass=MASS))
+    add("herdt_rollout_launcher/push_type", lambda c: hl(c, push="shove", mass=MASS))
+    add("herdt_rollout_launcher/trace_mass_none", lambda c: hl(c, trace=c.trace))
+    add("herdt_rollout_launcher/foot_shape", lambda c: hl(c, push=c.push, mass=MASS,
+                                                          foot=c.t(B, n, 3)))
+
+    # Plan.trace_margin
+    tm = lambda c, trace=None, plan="up", **kw: getattr(c, plan).trace_margin(  # noqa: E731
+        c.hist, c.zmax, c.zmin, c.trace if trace is None else trace, **{"mass": MASS, **kw})
+    add("trace_margin/trace_type", lambda c: tm(c, trace=c.push))
+    add("trace_margin/rows", lambda c: tm(c, draws=2))
+    add("trace_margin/rows_type_first", lambda c: tm(c, trace="trace", draws=2))
+    add("trace_margin/draws_zero", lambda c: tm(c, draws=0))
+    add("trace_margin/draws_bool", lambda c: tm(c, draws=True))
+    add("trace_margin/draws_float", lambda c: tm(c, draws=1.0))
+    add("trace_margin/mass_none", lambda c: tm(c, mass=None))
+    add("trace_margin/mass_zero", lambda c: tm(c, mass=0.0))
+    add("trace_margin/lengths", lambda c: tm(c, lengths=three))
+    add("trace_margin/scale_shape", lambda c: tm(c, scale=c.t(B, 2)))
+    add("trace_margin/limit_dtype", lambda c: tm(c, limit=c.t(B, 1, 2, dtype=torch.int64)))
+    add("trace_margin/hist_numpy",
+        lambda c: c.up.trace_margin(np.zeros((B, n, 2, 3)), c.zmax, c.zmin, c.trace, mass=MASS))
+    add("trace_margin/strict_plan", lambda c: tm(c, plan="sp"))
+
     # ZMPController
+    for name in ("generate_state_trajectory_batch", "generate_com_trajectory_batch"):
+        sb = lambda c, name=name, **kw: getattr(c.cu, name)(None, c.zmax, c.zmin,  # noqa: E731
+                                                            trace=c.trace, **kw)
+        add(f"controller/{name}/trace_and_F_ext", lambda c, sb=sb: sb(c, F_ext=[1.0, 1.0]))
+        add(f"controller/{name}/trace_and_push", lambda c, sb=sb: sb(c, push=c.push))
+        add(f"controller/{name}/trace_and_force_step", lambda c, sb=sb: sb(c, force_step=1))
+        add(f"controller/{name}/trace_and_walk_lengths",
+            lambda c, sb=sb: sb(c, walk_lengths=[n, n]))
+        add(f"controller/{name}/F_ext_push_and_trace",
+            lambda c, sb=sb: sb(c, F_ext=[1.0, 1.0], push=c.push))
+    add("controller/state_batch/trace_type",
+        lambda c: c.cu.generate_state_trajectory_batch(c.x0, c.zmax, c.zmin, trace=c.push))
+    hb = lambda c, **kw: c.ch.generate_com_trajectory_herdt_batch(None, c.v, c.st,  # noqa: E731
+                                                                  trace=c.trace, **kw)
+    add("controller/herdt_batch/trace_and_F_ext", lambda c: hb(c, F_ext=[1.0, 1.0]))
+    add("controller/herdt_batch/trace_and_push", lambda c: hb(c, push=c.push))
+    add("controller/herdt_batch/F_ext_push_and_trace",
+        lambda c: hb(c, F_ext=[1.0, 1.0], push=c.push))
+    for tag, ctl in (("up", "cu"), ("sp", "cs")):
+        ct = lambda c, ctl=ctl, trace=None, **kw: getattr(c, ctl).critical_force(  # noqa: E731
+            c.zmax, c.zmin, iters=0, trace=c.trace if trace is None else trace, **kw)
+        add(f"controller/critical_force/{tag}/trace_type", lambda c, ct=ct: ct(c, trace=c.push))
+        add(f"controller/critical_force/{tag}/trace_and_force_step",
+            lambda c, ct=ct: ct(c, force_step=1))
+        add(f"controller/critical_force/{tag}/trace_and_direction",
+            lambda c, ct=ct: ct(c, direction=-1))
+        add(f"controller/critical_force/{tag}/trace_and_signs",
+            lambda c, ct=ct: ct(c, direction=[1, 1]))
+        add(f"controller/critical_force/{tag}/trace_and_planar",
+            lambda c, ct=ct: ct(c, direction=[[0.0, 1.0]]))
+        add(f"controller/critical_force/{tag}/trace_and_duration",
+            lambda c, ct=ct: ct(c, duration=2))
+        add(f"controller/critical_force/{tag}/trace_and_profile",
+            lambda c, ct=ct: ct(c, profile=[1.0]))
+        add(f"controller/critical_force/{tag}/trace_fused", lambda c, ct=ct: ct(c, fused=True))
+        add(f"controller/critical_force/{tag}/trace_sizes",
+            lambda c, ct=ct: ct(c, trace=PushTrace(np.ones((3, 2)), 1)))
+        add(f"controller/critical_force/{tag}/trace_bad_duration",
+            lambda c, ct=ct: ct(c, duration=0))
+    ch = lambda c, trace=None, max_dcm_dev=1.0, **kw: c.ch.critical_force_herdt(  # noqa: E731
+        c.v, c.st, max_dcm_dev, iters=0, trace=c.trace if trace is None else trace, **kw)
+    add("controller/critical_force_herdt/trace_type", lambda c: ch(c, trace=c.push))
+    add("controller/critical_force_herdt/trace_and_force_step", lambda c: ch(c, force_step=1))
+    add("controller/critical_force_herdt/trace_and_direction", lambda c: ch(c, direction=-1))
+    add("controller/critical_force_herdt/trace_and_signs", lambda c: ch(c, direction=[1, 1]))
+    add("controller/critical_force_herdt/trace_and_planar",
+        lambda c: ch(c, direction=[[0.0, 1.0]]))
+    add("controller/critical_force_herdt/trace_and_duration", lambda c: ch(c, duration=2))
+    add("controller/critical_force_herdt/trace_and_profile", lambda c: ch(c, profile=[1.0]))
+    add("controller/critical_force_herdt/trace_max_dcm_dev", lambda c: ch(c, max_dcm_dev=None))
+    add("controller/critical_force_herdt/trace_F_hi", lambda c: ch(c, F_hi=0.0))
+    add("controller/critical_force_herdt/trace_sizes",
+        lambda c: ch(c, trace=PushTrace(np.ones((3, 2)), 1)))
+    # ... and the sizing of critical_force_herdt without one, in its own words
+    nh = lambda c, *a, **kw: c.ch.critical_force_herdt(*a, 1.0, iters=0, **kw)  # noqa: E731
+    add("controller/critical_force_herdt/sizes", lambda c: nh(c, c.v, c.st, force_step=three))
+    add("controller/critical_force_herdt/sizes_planar",
+        lambda c: nh(c, c.v, c.st, direction=[[1, 0], [0, 1], [1, 1]]))
+    add("controller/critical_force_herdt/sizes_first_force_step",
+        lambda c: nh(c, c.v[0], c.st[0], force_step=three, direction=[1, 1]))
+    add("controller/critical_force_herdt/sizes_direction_before_lengths",
+        lambda c: nh(c, c.v[0], c.st[0], direction=[1, 1], walk_lengths=three))
+    add("controller/critical_force_herdt/sizes_x_init",
+        lambda c: nh(c, c.v[0], c.st[0], x_init=np.zeros((3, 2, 3)), force_step=[1, 1]))
+    ctm = lambda c, ctl="cu", trace=None, **kw: getattr(c, ctl).trace_margin(  # noqa: E731
+        c.zmax, c.zmin, c.trace if trace is None else trace, **kw)
+    add("controller/trace_margin/trace_type", lambda c: ctm(c, trace=c.push))
+    add("controller/trace_margin/draws", lambda c: ctm(c, draws=0))
+    add("controller/trace_margin/rows_multiple",
+        lambda c: ctm(c, trace=PushTrace(np.ones((3, 2)), 1), draws=2))
+    add("controller/trace_margin/rows_named", lambda c: ctm(c, draws=2))
+    add("controller/trace_margin/strict", lambda c: ctm(c, ctl="cs"))
     add("controller/state_batch/F_ext_and_push",
         lambda c: c.cu.generate_state_trajectory_batch(None, c.zmax, c.zmin, F_ext=[1.0, 1.0],
                                                        push=c.push))
@@ -280,6 +414,20 @@ def launchers(c):
                                             profile=[1.0, 0.5]), mass=MASS),
         "rollout_launcher/strict_push": c.sp.rollout_launcher(c.zmax, c.zmin, c.x0, push=c.push,
                                                               mass=MASS),
+        "rollout_launcher/trace": c.up.rollout_launcher(c.zmax, c.zmin, c.x0, trace=c.trace,
+                                                        mass=MASS),
+        "rollout_launcher/trace_steps_device": c.up.rollout_launcher(
+            c.zmax, c.zmin, c.x0, trace=PushTrace.from_velocity_steps(
+                torch.full((B, 3, 2), 1e-3, dtype=torch.float64, device=c.dev), np.array([0, 1]))),
+        "rollout_launcher/strict_trace": c.sp.rollout_launcher(c.zmax, c.zmin, c.x0,
+                                                               trace=c.trace, mass=MASS),
+        "herdt_rollout_launcher/push": c.up.herdt_rollout_launcher(
+            c.hprm, c.hv, c.hst, c.hnb, c.x0, push=c.push, mass=MASS),
+        "herdt_rollout_launcher/push_steps_profile": c.up.herdt_rollout_launcher(
+            c.hprm, c.hv, c.hst, c.hnb, c.x0, mass=MASS,
+            push=Push(1.0, [[1.0, 1.0]], np.array([0, 1]), duration=2, profile=[1.0, 0.5])),
+        "herdt_rollout_launcher/trace": c.up.herdt_rollout_launcher(
+            c.hprm, c.hv, c.hst, c.hnb, c.x0, trace=c.trace, mass=MASS),
         "rollout_metrics_launcher": c.up.rollout_metrics_launcher(
             c.zmax, c.zmin, c.x0, kick=kick, kick_step=[0, 1], lengths=[n, n - 1]),
     }
